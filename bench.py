@@ -10,7 +10,10 @@ precision), random-init weights, synthetic uint8 CIFAR-10-shaped images resident
 whole step is captured once as a hipGraph and replayed (eager fallback if capture fails).
 
 Scaling: ``value`` is for ``--scaling`` (weak by default: 256 images per GPU per step, the
-reference's per-process batch at W=1). For N > 1 the line also carries ``strong``: the reference's
+reference's per-process batch at W=1). A plain run measures that headline alone; ``--full`` adds the
+secondary measurements (N = 1: the strict-fp32 engine, the per-GPU strong-scaling points, ResNet-50;
+N > 1: the phases below). ``--dump-outputs DIR`` writes what the last timed step computed as
+``DIR/<name>.npy``. With ``--full`` and N > 1 the line also carries ``strong``: the reference's
 own rule -- a fixed global batch of 256 split ``int(256/W)`` per rank
 (``/root/reference/src/Part 2a/main.py:22``) -- and ``exposed_comm_ms``: ms/step with sync minus
 ms/step of the same step without gradient sync (the part of the all-reduce backward did not hide).
@@ -65,12 +68,21 @@ def parse(argv=None):
     p.add_argument("--strategy", default="ddp", choices=["ddp", "bucketed_overlap", "allreduce_blocking",
                                                           "gather_scatter"])
     p.add_argument("--no-graph", action="store_true", help="eager steps instead of one hipGraph replay per step")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run the secondary measurements (N = 1: the strict-fp32 engine, "
+                        "the per-GPU strong-scaling points, ResNet-50; N > 1: the no-sync step for exposed comm, "
+                        "every sync strategy at the strong-scaling rule, ResNet-50). Without it the run is the "
+                        "headline alone: set up, warm up, time --steps steps, print the record")
     p.add_argument("--no-extra", action="store_true",
-                   help="skip the secondary measurements (strong-scaling point, no-sync step for exposed comm)")
+                   help="with --full: skip the secondary measurements after all (a plain run has none)")
     p.add_argument("--extras", default="all",
                    help="N > 1: comma list of the secondary phases to run (no_sync, strong_ddp, strong_no_sync, "
                         "strong_allreduce_blocking, strong_bucketed_overlap, resnet50_ddp, resnet50_no_sync, "
-                        "strong_gather_scatter), default all")
+                        "strong_gather_scatter); a list implies --full, whose default is all of them")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step of the headline computed (loss, "
+                        "logits, the updated parameters and BN buffers) as DIR/<name>.npy in float32, at most "
+                        "64 MB in all (a fixed seeded sample of the larger tensors when the whole is more)")
     p.add_argument("--backend", default="native", choices=["native", "torch"],
                    help="torch = stock PyTorch-ROCm ops + torch DDP (comparison only)")
     p.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
@@ -94,7 +106,10 @@ def parse(argv=None):
     p.add_argument("--dist-backend", default="auto", choices=["auto", "gloo"],
                    help="gloo: rehearse the multi-rank GPU path on ONE GPU (all ranks share cuda:0, gradients "
                         "over gloo; not a performance mode)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    args.full = args.full or args.extras != "all"  # naming secondary phases asks for them
+    args.no_extra = args.no_extra or not args.full  # the secondary measurements exist under --full only
+    return args
 
 
 # ---------------------------------------------------------------------------------- launcher
@@ -242,6 +257,8 @@ class _Run:
         self.opt.step()
         if self.break_capture and self.torch.cuda.is_current_stream_capturing():
             loss.item()  # test hook: a host read of a captured value invalidates the capture
+        # what the step hands its caller (a captured step rewrites these same tensors at every replay)
+        self.last = (out.detach(), loss.detach())
         return loss
 
     def prepare(self, warmup, dbg):
@@ -403,6 +420,16 @@ class _Run:
             val += t.to(torch.float64).sum()
         return torch.stack([bits, val.view(torch.int64)])
 
+    def outputs(self):
+        """What the last step handed its caller, by name: the loss, the logits, and the training state
+        the step updated in place (every parameter and BN buffer)."""
+        out, loss = self.last
+        named = {"loss": loss, "logits": out}
+        mod = getattr(self.model, "module", self.model)
+        named.update({f"param.{n}": p.detach() for n, p in mod.named_parameters()})
+        named.update({f"buffer.{n}": b.detach() for n, b in mod.named_buffers()})
+        return named
+
     def release(self):
         if self.graph is not None:
             self.graph.reset()
@@ -415,14 +442,41 @@ class _Run:
             self.sync = None
 
 
-def _measure(args, world, rank, dev, lb, dbg, dist, steps=None, warmup=None, full=False, **kw):
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs writes at most this much array data (the limit is 64 MB)
+DUMP_WHOLE_ELEMS = 4096  # tensors up to this size are always written whole
+
+
+def _dump_outputs(path, named):
+    """Write ``named`` (name -> tensor) as ``path/<name>.npy`` in float32. When the whole is over the
+    budget, every tensor above DUMP_WHOLE_ELEMS is cut to the same fraction of its elements, picked
+    (sorted, without replacement) by a generator seeded from the tensor's position: the same
+    arguments pick the same elements in every run and every build."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrs = {n: t.detach().to("cpu").float().contiguous().numpy() for n, t in named.items()}
+    big = sum(a.size for a in arrs.values() if a.size > DUMP_WHOLE_ELEMS)
+    small = sum(a.size for a in arrs.values() if a.size <= DUMP_WHOLE_ELEMS)
+    frac = min(1.0, max(0.0, DUMP_BUDGET_BYTES / 4 - small) / max(1, big))
+    for i, (name, a) in enumerate(arrs.items()):
+        if frac < 1.0 and a.size > DUMP_WHOLE_ELEMS:
+            k = max(DUMP_WHOLE_ELEMS, int(a.size * frac))
+            idx = np.sort(np.random.default_rng(1000 + i).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def _measure(args, world, rank, dev, lb, dbg, dist, steps=None, warmup=None, full=False, dump=None, **kw):
     """ms/step of one more (local batch, model, sync) point, measured like the headline. With
-    ``full``: (ms, hipgraph, replicas_identical, bucket plan)."""
+    ``full``: (ms, hipgraph, replicas_identical, bucket plan). ``dump``: directory for the last
+    timed step's outputs (--dump-outputs)."""
     r = _Run(args, world, rank, dev, lb, **kw)
     r.prepare(args.warmup if warmup is None else warmup, dbg)
     _maybe_fault(r)
     ms = r.time(args.steps if steps is None else steps, dist)
     hg = r.graph is not None
+    if dump:
+        _dump_outputs(dump, r.outputs())
     _LAST_GRAPH_COLLECTIVES[0] = r.graph_collectives if hg else None
     rep = r.replicas_identical(dist) if full else None
     plan = r.bucket_plan() if full else None
@@ -576,8 +630,9 @@ class _Ctx:
         kw = dict(sync_grads=spec["sync"], strategy=spec.get("strategy"), model_name=spec.get("model"))
         if "image_size" in spec:
             kw["image_size"] = spec["image_size"]
+        dump = args.dump_outputs if spec.get("headline") and self.rank == 0 else None  # replicas are identical
         res = _measure(args, self.world, self.rank, self.dev, spec["lb"], self.dbg, self.dist, steps=spec.get("steps"),
-                       warmup=spec.get("warmup"), full=bool(spec.get("full")), **kw)
+                       warmup=spec.get("warmup"), full=bool(spec.get("full")), dump=dump, **kw)
         out = {"ms": res[0], "hipgraph": res[1]}
         if spec.get("full"):
             out["replicas_identical"], out["buckets"] = res[2], res[3]
@@ -952,7 +1007,7 @@ def single_main(args) -> int:
     cdp, dist, dev, dbg = ctx.cdp, ctx.dist, ctx.dev, ctx.dbg
     main_lb = args.local_batch if args.scaling == "weak" else max(1, args.global_batch)
     os.environ["CDP_BENCH_PHASE"] = "headline"
-    head = ctx.point({"lb": main_lb, "sync": True, "full": True, "strategy": args.strategy})
+    head = ctx.point({"lb": main_lb, "sync": True, "full": True, "strategy": args.strategy, "headline": True})
     if args.backend == "native" and not ctx.cpu:
         _dump_gemm_log(cdp)
     head.update(ranks_seen=1, comm="none", engine="reference" if ctx.cpu else _conv_gemm_engine(args.backend),

@@ -3,7 +3,7 @@
 For every strategy (gather_scatter = Part 2a, allreduce_blocking = Part 2b, bucketed_overlap =
 hook-bucketed overlap, ddp = Part 3) and every N in --gpus, runs
 
-    python bench.py --gpus N --strategy S [--model M --bucket-cap-mb C] --steps K --warmup W
+    python bench.py --full --gpus N --strategy S [--model M --bucket-cap-mb C] --steps K --warmup W
 
 (bench.py starts the N rank processes itself) and collects img/s for weak scaling (256 images per
 GPU) and the reference's strong scaling (global 256 split int(256/N), /root/reference/src/Part
@@ -28,7 +28,7 @@ STRATEGIES = ["gather_scatter", "allreduce_blocking", "bucketed_overlap", "ddp"]
 
 
 def run_one(n, strategy, args, cap=None):
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--strategy", strategy,
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", str(n), "--strategy", strategy,
            "--steps", str(args.steps), "--warmup", str(args.warmup), "--model", args.model]
     if cap is not None:
         cmd += ["--bucket-cap-mb", str(cap)]

@@ -109,7 +109,7 @@ def test_capture_failure_on_one_rank_makes_every_rank_eager():
     env = dict(os.environ, PYTHONPATH=repo, CDP_BENCH_BREAK_CAPTURE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--full",
                         "--strategy", "allreduce_blocking", "--steps", "2", "--warmup", "1", "--local-batch", "8",
                         "--dataset-size", "64", "--extras", "no_sync,strong_no_sync"],
                        env=env, capture_output=True, text=True, timeout=240, cwd=repo)

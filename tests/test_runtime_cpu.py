@@ -307,7 +307,7 @@ def test_bench_self_launches_ranks_cpu():
     reference's whole multi-process experiment: every sync strategy at its strong-scaling rule
     (int(global / W) images per rank), each with ms/step, exposed sync, scaling_eff and a
     bit-identical-replicas check -- BASELINE.md's Part 2a / 2b / 3 rows map onto these keys."""
-    r = _bench(["--gpus", "2", "--device", "cpu", "--steps", "2", "--warmup", "1", "--local-batch", "4",
+    r = _bench(["--gpus", "2", "--device", "cpu", "--full", "--steps", "2", "--warmup", "1", "--local-batch", "4",
                 "--global-batch", "16", "--dataset-size", "64"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -393,7 +393,7 @@ def test_bench_failed_extra_keeps_the_headline(fault, phase):
     import time
 
     t0 = time.monotonic()
-    r = _bench(["--gpus", "2", "--device", "cpu", "--steps", "1", "--warmup", "1", "--local-batch", "2",
+    r = _bench(["--gpus", "2", "--device", "cpu", "--full", "--steps", "1", "--warmup", "1", "--local-batch", "2",
                 "--global-batch", "4", "--dataset-size", "16",
                 "--extras", "no_sync,strong_allreduce_blocking,strong_bucketed_overlap"],
                env_extra={"CDP_BENCH_FAULT": f"{phase}:1:{fault}", "CDP_BENCH_PHASE_LIMIT_S": "30"}, timeout=300)
@@ -427,7 +427,7 @@ def test_bench_failed_extra_keeps_the_headline(fault, phase):
 def test_bench_time_budget_skips_extras():
     """When the budget is spent before an extra could finish, that extra is skipped by agreement (every
     rank the same way) and the headline is still printed."""
-    r = _bench(["--gpus", "2", "--device", "cpu", "--steps", "1", "--warmup", "1", "--local-batch", "2",
+    r = _bench(["--gpus", "2", "--device", "cpu", "--full", "--steps", "1", "--warmup", "1", "--local-batch", "2",
                 "--global-batch", "4", "--dataset-size", "16", "--extras", "no_sync,strong_allreduce_blocking"],
                env_extra={"CDP_BENCH_BUDGET_S": "1", "CDP_BENCH_PHASE_LIMIT_S": "30"}, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -448,3 +448,66 @@ def test_bench_detects_diverged_replicas(strategy):
     assert r.returncode != 0
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert rec["replicas_identical"] is False
+
+
+def _npy_dir(path):
+    return {n: np.load(os.path.join(path, n)) for n in sorted(os.listdir(path))}
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full a run measures the headline and nothing else (N = 2: one phase, no strategies
+    block, no no-sync step), --steps is the number of timed steps the record divides by, and
+    --dump-outputs writes the last timed step's outputs."""
+    r = _bench(["--gpus", "2", "--device", "cpu", "--steps", "2", "--warmup", "1", "--local-batch", "2",
+                "--dataset-size", "16", "--dump-outputs", str(tmp_path / "d")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert [p["name"] for p in rec["phases"]] == ["headline"]
+    for k in ("strategies", "strong", "exposed_comm_ms", "resnet50", "no_sync", "scaling_eff"):
+        assert k not in rec, k
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["replicas_identical"] is True
+    assert rec["value"] == pytest.approx(4 / rec["ms_per_step"] * 1e3, rel=1e-3)
+    out = _npy_dir(str(tmp_path / "d"))
+    assert out["loss.npy"].shape == () and out["logits.npy"].shape == (2, 10)
+    assert out["param.fc1.weight.npy"].shape == (10, 512)
+
+
+def test_bench_dump_outputs_repeats_bit_for_bit(tmp_path):
+    """Same arguments, same inputs: two N = 1 runs dump the same arrays (float32, every parameter
+    and buffer of VGG-11 whole, within the 64 MB limit), and more timed steps give other values."""
+    args = ["--gpus", "1", "--device", "cpu", "--warmup", "1", "--local-batch", "4", "--dataset-size", "32"]
+    outs = []
+    for name, steps in (("a", "2"), ("b", "2"), ("c", "3")):
+        r = _bench(args + ["--steps", steps, "--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs.append(_npy_dir(str(tmp_path / name)))
+    a, b, c = outs
+    assert list(a) == list(b) == list(c) and "loss.npy" in a and "logits.npy" in a
+    assert sum(1 for n in a if n.startswith("param.")) == 34
+    assert sum(x.nbytes for x in a.values()) <= 64 * 10**6
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        np.testing.assert_array_equal(a[n], b[n], err_msg=n)
+    assert a["param.layers.0.weight.npy"].shape == (64, 3, 3, 3)
+    assert not np.array_equal(a["param.fc1.weight.npy"], c["param.fc1.weight.npy"])
+
+
+def test_bench_dump_samples_large_outputs(tmp_path):
+    """Over the budget every large tensor is cut to the same seeded, sorted choice of its elements;
+    small ones stay whole."""
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    named = {"big0": torch.randn(9_000_000, generator=g), "small": torch.arange(10.0),
+             "big1": torch.randn(3000, 3000, generator=g)}
+    bench._dump_outputs(str(tmp_path / "a"), named)
+    bench._dump_outputs(str(tmp_path / "b"), named)
+    a, b = _npy_dir(str(tmp_path / "a")), _npy_dir(str(tmp_path / "b"))
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    np.testing.assert_array_equal(a["small.npy"], np.arange(10.0, dtype=np.float32))
+    for n in ("big0.npy", "big1.npy"):
+        np.testing.assert_array_equal(a[n], b[n])
+        assert a[n].ndim == 1 and 0.6 < a[n].size / 9_000_000 < 0.72  # 48 MiB / 72 MB of big tensors
+    assert np.isin(a["big0.npy"], named["big0"].numpy()).all()
