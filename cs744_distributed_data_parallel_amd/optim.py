@@ -12,6 +12,16 @@ kernel (float4, fma order matching ATen's ``add(alpha=...)``) instead of one lau
 ``zero_grad`` zeroes the gradient arena in place (the arena views stay attached, which keeps the
 bucketed reducer zero-copy). The learning rate can live on the device (``lr_tensor``) so a captured
 hipGraph step follows an LR schedule without re-capture.
+
+Gradient clipping (``max_grad_norm``) and non-finite step skipping (``skip_nonfinite``) ride in the
+same launch: one extra dispatch writes fp64 partial sums of squares of the gradient arena, and every
+workgroup of the SGD kernel derives the global norm and ``coef = min(max_grad_norm / (norm + 1e-6), 1)``
+from them in its prologue -- no second pass over the gradients, no host sync, so a captured step
+clips with the norm of each replay. Unlike ``torch.nn.utils.clip_grad_norm_``, the fused path leaves
+``p.grad`` UNSCALED (the coefficient is applied as the kernel reads the gradient); the reference
+paths (CPU, ``force_reference``, per-parameter launches) scale it in place as torch does. With
+``skip_nonfinite`` a step whose norm is inf / NaN leaves parameters and momentum bitwise unchanged
+(counted in ``skipped_steps``); :func:`clip_grad_norm_` is the stand-alone, in-place form.
 """
 from __future__ import annotations
 
@@ -34,6 +44,8 @@ class SGD(Optimizer):
         *,
         maximize: bool = False,
         flat: bool = True,
+        max_grad_norm: float | None = None,
+        skip_nonfinite: bool = False,
     ):
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -43,6 +55,8 @@ class SGD(Optimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
         defaults = dict(
             lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
             maximize=maximize, foreach=None, differentiable=False, fused=None,
@@ -63,6 +77,87 @@ class SGD(Optimizer):
         if flat and all_params and all_params[0].is_cuda:
             self._arena = arena_for(all_params)
             self._arena.on_relayout(self._on_relayout)
+        # gradient-norm clipping / non-finite step skipping: optimizer attributes, not param_group
+        # entries, so state_dict() stays torch's
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip_part = self._clip_stats = None
+        self._clip_fused = False
+        if self.skip_nonfinite and any(g["dampening"] != 0 for g in self.param_groups):
+            # a skipped first momentum step zeroes the buffer and the next computes
+            # buf = (1 - dampening) * d_p: torch's first-step buf = d_p only for dampening 0
+            raise ValueError("skip_nonfinite requires zero dampening")
+        if self._clip_enabled and all_params:
+            # allocated here, never inside a capture: the partial sums of squares of the norm kernel
+            # and {norm, coef, skipped steps} (device-side; grad_norm / clip_coef / skipped_steps)
+            dev = all_params[0].device
+            self._clip_stats = torch.zeros(4, dtype=torch.float32, device=dev)
+            if dev.type == "cuda":
+                self._clip_part = torch.zeros(1024, dtype=torch.float64, device=dev)
+
+    # ------------------------------------------------------------------ gradient clipping
+    @property
+    def _clip_enabled(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    @property
+    def grad_norm(self):
+        """Global gradient 2-norm of the last step: a 0-dim device view (reading it here never syncs);
+        None unless ``max_grad_norm`` / ``skip_nonfinite`` is set."""
+        return self._clip_stats[0] if self._clip_stats is not None else None
+
+    @property
+    def clip_coef(self):
+        """``min(max_grad_norm / (grad_norm + 1e-6), 1)`` of the last step (0-dim device view)."""
+        return self._clip_stats[1] if self._clip_stats is not None else None
+
+    @property
+    def skipped_steps(self):
+        """Steps skipped for an inf / NaN gradient norm so far (0-dim device view, a float count)."""
+        return self._clip_stats[2] if self._clip_stats is not None else None
+
+    def _clip_fusable(self) -> bool:
+        """Whether this step runs as one flat launch (or the split plan's launches) over one arena
+        range, so the clip can ride in it: one param group, all of its parameters with gradients, one
+        contiguous arena run, momentum buffers all first or all later."""
+        if self._arena is None or self._clip_part is None or len(self.param_groups) != 1 or _native.force_reference():
+            return False
+        group = self.param_groups[0]
+        params = group["params"]
+        if not params or any(p.grad is None or not p.is_cuda for p in params):
+            return False
+        if self._arena.contiguous_range(params) is None:
+            return False
+        if any(getattr(p, "_cdp_arena", None) is not self._arena for p in params):
+            return False
+        if group["momentum"] != 0.0:
+            firsts = self._first_flags(params)
+            if any(firsts) and not all(firsts):
+                return False
+        return True
+
+    def _clip_reference(self, params) -> bool:
+        """The clip outside the fused launch (CPU, ``force_reference``, per-parameter launches):
+        total norm and coefficient with torch ops exactly as ``torch.nn.utils.clip_grad_norm_``
+        computes them, gradients scaled in place as it does. Returns True when the step is to be
+        skipped (``skip_nonfinite`` and an inf / NaN norm; a host read)."""
+        grads = [p.grad for p in params]
+        norms = [torch.linalg.vector_norm(g, 2.0) for g in grads]
+        total = torch.linalg.vector_norm(torch.stack([n.to(norms[0].device) for n in norms]), 2.0)
+        st = self._clip_stats
+        st[0].copy_(total)
+        if self.skip_nonfinite and not bool(torch.isfinite(total)):
+            st[1].fill_(float("nan") if self.max_grad_norm is not None else 1.0)
+            st[2] += 1
+            return True
+        if self.max_grad_norm is None:
+            st[1].fill_(1.0)
+            return False
+        coef = torch.clamp(self.max_grad_norm / (total + 1e-6), max=1.0)
+        st[1].copy_(coef)
+        for g in grads:
+            g.mul_(coef.to(g.device))
+        return False
 
     def _on_relayout(self, arena):
         # the arena moved the momentum values with their parameters; re-point the state views
@@ -140,9 +235,18 @@ class SGD(Optimizer):
             if done:
                 raise RuntimeError(f"overlapped optimizer step: only {done} of {ov['n']} buckets were stepped")
         self._counter_pending = self._step_counter
+        skip = False
+        self._clip_fused = False
+        if self._clip_enabled:
+            # the norm is over the whole model: inside the one flat launch where the step is one (see
+            # _flat_step), otherwise up front with torch ops
+            self._clip_fused = self._clip_fusable()
+            if not self._clip_fused:
+                with_grad = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+                skip = bool(with_grad) and self._clip_reference(with_grad)
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
-            if not params:
+            if not params or skip:
                 continue
             if self._arena is not None:
                 self._arena.prep_valid = None  # re-marked below only by a fused step
@@ -179,11 +283,13 @@ class SGD(Optimizer):
         bucket for the reducer's ``set_bucket_step`` -- the SGD of that range, run on the reducer's
         step stream right after the bucket's all-reduce -- or None when the step cannot be split
         this iteration (several param groups, parameters outside one arena run, first and later
-        momentum steps mixed, no native kernels). The next ``step()`` then only does the
+        momentum steps mixed, no native kernels, ``max_grad_norm`` / ``skip_nonfinite`` set). The next ``step()`` then only does the
         bookkeeping, provided the reducer stepped every bucket; hyperparameters are those at the
         time of this call (the forward), the first-step momentum rule (buf = d_p) is kept."""
         if self._arena is None or len(self.param_groups) != 1 or _native.force_reference():
             return None
+        if self._clip_enabled:
+            return None  # the clip needs the norm of the whole model: the step runs whole at step()
         group = self.param_groups[0]
         params, arena = group["params"], self._arena
         if len(params) != len(arena.params) or any(not p.is_cuda for p in params):
@@ -289,6 +395,8 @@ class SGD(Optimizer):
             self._flat_step(C, arena, s, e, None, lr_t, lr, 0.0, damp, wd, nest, True, maxim)
             return
         # general path: one launch per parameter (non-arena / partial groups)
+        if self._clip_fused:
+            raise RuntimeError("gradient clipping was planned into a flat step that did not run")
         for p in params:
             st = self.state[p]
             buf = st.get("momentum_buffer")
@@ -318,23 +426,35 @@ class SGD(Optimizer):
         weight |max| partials and W^T (FlatArena.prep_plan_for) when a model registered them."""
         plan = arena.prep_plan_for(s, e) if self.fused_prep else None
         ctr, self._counter_pending = self._counter_pending, None
+        clip = {}
+        if self._clip_fused:
+            # one extra dispatch: the partial sums of squares of the whole range (the arena's pad
+            # floats are zero); every SGD launch below derives the same norm / coefficient from them
+            # in its prologue. p.grad itself is left unscaled.
+            part = self._clip_part[:C.grad_norm_parts(e - s)]
+            C.grad_sumsq(arena.grad[s:e], part)
+            clip = dict(clip_part=part, max_norm=self.max_grad_norm if self.max_grad_norm is not None else float("inf"),
+                        stats=self._clip_stats, skip_nonfinite=self.skip_nonfinite)
         if plan is None:
-            C.sgd_step(arena.data[s:e], arena.grad[s:e], mom, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, ctr)
+            C.sgd_step(arena.data[s:e], arena.grad[s:e], mom, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, ctr,
+                       **clip)
             return
         if "subs" in plan:  # the split plan of an overlapped step (same buffers): its ranges in turn
             last = len(plan["ranges"]) - 1
             for k, ((a, b), sub) in enumerate(zip(plan["ranges"], plan["subs"])):
                 mk = mom[a - s:b - s] if mom is not None else None
                 c = ctr if k == last else None
+                ck = clip if k == last or not clip else dict(clip, stats=None)  # stats written once
                 if sub is None:
-                    C.sgd_step(arena.data[a:b], arena.grad[a:b], mk, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, c)
+                    C.sgd_step(arena.data[a:b], arena.grad[a:b], mk, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, c,
+                               **ck)
                 else:
                     C.sgd_step_prep(arena.data[a:b], arena.grad[a:b], mk, lr_t, lr, m, damp, wd, 1.0, nest, first,
-                                    maxim, sub["desc"], sub["meta"], plan["amax"], c)
+                                    maxim, sub["desc"], sub["meta"], plan["amax"], c, **ck)
             arena.prep_mark_valid()
             return
         C.sgd_step_prep(arena.data[s:e], arena.grad[s:e], mom, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim,
-                        plan["desc"], plan["meta"], plan["amax"], ctr)
+                        plan["desc"], plan["meta"], plan["amax"], ctr, **clip)
         arena.prep_mark_valid()
 
     def _step_reference(self, group, params):
@@ -353,3 +473,59 @@ class SGD(Optimizer):
                     buf.mul_(m).add_(d_p, alpha=1 - damp)
                 d_p = d_p.add(buf, alpha=m) if group["nesterov"] else buf
             p.add_(d_p, alpha=-lr)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` (same signature, same return: the total norm as a tensor;
+    gradients scaled in place) in two launches where it can be: for the 2-norm of GPU parameters whose
+    gradients are one contiguous run of a :class:`~.utils.arena.FlatArena`, one kernel writes fp64
+    partial sums of squares of the run and a second derives ``coef = min(max_norm / (norm + 1e-6), 1)``
+    from them and scales the run. Anything else (another norm type, parameters outside an arena,
+    CPU) is handed to torch's implementation. ``error_if_nonfinite=True`` reads the norm on the host
+    and is refused while a stream is capturing."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    rng = _arena_grad_range(parameters) if float(norm_type) == 2.0 else None
+    if rng is None:
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=norm_type,
+                                              error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    arena, s, e = rng
+    C = _native.lib()
+    g = arena.grad[s:e]
+    part = torch.empty(C.grad_norm_parts(e - s), dtype=torch.float64, device=g.device)
+    stats = torch.empty(3, dtype=torch.float32, device=g.device)
+    C.grad_sumsq(g, part)
+    if error_if_nonfinite:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("clip_grad_norm_(error_if_nonfinite=True) reads the norm on the host: "
+                               "not possible while the stream is capturing")
+        total = part.sum().sqrt().float()
+        if not bool(torch.isfinite(total)):
+            raise RuntimeError(
+                f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be "
+                "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                "`error_if_nonfinite=False`")
+    C.clip_scale(g, part, float(max_norm), stats)
+    return stats[0]
+
+
+def _arena_grad_range(parameters):
+    """(arena, start, end) when the parameters with a gradient are GPU parameters of one arena, cover
+    one gap-free run of it and each ``p.grad`` is its arena view; else None."""
+    ps = [p for p in parameters if p.grad is not None]
+    if not ps or _native.force_reference() or any(not p.is_cuda for p in ps):
+        return None
+    arena = getattr(ps[0], "_cdp_arena", None)
+    if arena is None or arena.grad is None or any(getattr(p, "_cdp_arena", None) is not arena for p in ps):
+        return None
+    if len({id(p) for p in ps}) != len(ps) or arena.grad.dtype != torch.float32:
+        return None
+    base, es = arena.grad.data_ptr(), arena.grad.element_size()
+    if any(p.grad.data_ptr() != base + arena.offsets[p._cdp_index] * es or p.grad.dtype != torch.float32 for p in ps):
+        return None
+    rng = arena.contiguous_range(ps)
+    if rng is None or not _native.available():
+        return None
+    return arena, rng[0], rng[1]

@@ -106,7 +106,13 @@ class DistributedDataParallel(nn.Module):
         compute stream). ``optimizer.step()`` then only completes the bookkeeping. Applies to
         iterations with gradient sync on the RCCL communicator once the buckets are rebuilt in ready
         order (before that, and under ``no_sync``, the step runs whole as usual). The result is
-        bitwise the end-of-step SGD's. Needs this package's ``SGD`` over the module's parameters."""
+        bitwise the end-of-step SGD's. Needs this package's ``SGD`` over the module's parameters.
+
+        Anything done to the gradients between ``backward()`` and ``step()`` (an in-place rescale,
+        ``clip_grad_norm_``, ...) is not seen by an overlapped step: its SGD has already run inside
+        backward. An ``SGD`` built with ``max_grad_norm`` or ``skip_nonfinite`` needs the norm of
+        the whole model, so it declines the split and its step runs whole at ``step()``, after the
+        last all-reduce."""
         if not hasattr(optimizer, "bucket_steps"):
             raise TypeError("overlap_optimizer needs cs744_distributed_data_parallel_amd.SGD")
         self._step_opt = optimizer

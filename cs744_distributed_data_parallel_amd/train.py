@@ -90,6 +90,13 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 print_fn("Forward Pass time in iter {} is {}".format(iter_number, fwd / 20.0))
                 print_fn("Backward Pass time in iter {} is {}".format(iter_number, bwd / 20.0))
                 print_fn("Average Pass time in iter {} is {}".format(iter_number, (fwd + bwd) / 20.0))
+            if getattr(optimizer, "grad_norm", None) is not None:
+                # gradient clipping on: the window's last norm (stderr: stdout keeps the reference's lines)
+                import sys
+
+                print("[cdp] rank {}: grad norm in iter {} is {} (clip coef {}, skipped steps {})".format(
+                    rank, iter_number, float(optimizer.grad_norm), float(optimizer.clip_coef),
+                    int(optimizer.skipped_steps)), file=sys.stderr)
         if max_iters is not None and iter_number >= max_iters:
             break
         iter_number += 1
@@ -156,7 +163,8 @@ def run(rank, size, epochs, batch_size, args):
         model = DistributedDataParallel(model, bucket_cap_mb=args.bucket_cap_mb)
     elif strategy == "bucketed_overlap":
         sync = BucketedOverlap(model, bucket_cap_mb=args.bucket_cap_mb)
-    optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001)
+    optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
+                    max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
 
     start_epoch = 0
     if args.resume and args.checkpoint_dir:
@@ -255,6 +263,10 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=256, help="global batch (split int(B/W) per rank)")
     p.add_argument("--lr", type=float, default=0.1)
     p.add_argument("--iters", type=int, default=None, help="max iterations per epoch")
+    p.add_argument("--clip-grad-norm", type=float, default=None, metavar="FLOAT",
+                   help="clip the global gradient 2-norm to this value inside the fused optimizer step")
+    p.add_argument("--skip-nonfinite", action="store_true",
+                   help="skip an optimizer step whose gradients hold an inf or a NaN")
     p.add_argument("--bucket-cap-mb", type=float, default=None)
     p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
     p.add_argument("--seed", type=int, default=0)

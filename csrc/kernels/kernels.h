@@ -158,10 +158,24 @@ struct SgdPrepChunk {
   int n4, pad;
 };
 constexpr int kSgdPrepChunk4 = 1024;  // float4 per rest chunk (one workgroup)
+// Gradient-norm clip of a fused SGD step (grad_norm.hip, grad_clip.h). part == nullptr: no clipping,
+// the kernels run exactly as without this block. Otherwise part[0 .. nparts) are grad_sumsq_launch's
+// partial sums of squares over the WHOLE model's gradients; every workgroup derives
+// coef = min(max_norm / (norm + 1e-6), 1) from them and uses grad_scale * coef. stats (optional,
+// 3 floats): workgroup 0 writes norm, coef and, with skip_nonfinite and an inf / NaN norm, adds one
+// to stats[2]; such a step writes parameters and momentum back unchanged (a first momentum step:
+// zeros into the momentum) while the step counter and the weight preparation still happen.
+struct ClipArgs {
+  const double* part = nullptr;
+  int nparts = 0;
+  float max_norm = 0.f;
+  float* stats = nullptr;
+  int skip_nonfinite = 0;
+};
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
-                     bool maximize, hipStream_t st, long long* counter = nullptr);
+                     bool maximize, hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{});
 void slab_sum_launch(const float* slab, int S, long long n, float* dst, bool accumulate, hipStream_t st);
 void slab_sum_strided_launch(const float* slab, int S, long long n_src, int src_cols, int dst_cols, float* dst,
                              bool accumulate, hipStream_t st);
@@ -259,7 +273,30 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
 // counter (optional): a step counter the kernel advances by one (DeviceLoader.advance_with)
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
-                hipStream_t st, long long* counter = nullptr);
+                hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{});
+
+// grad_norm.hip: the global gradient norm of a flat fp32 range, in two deterministic stages.
+// grad_sumsq_launch writes P = grad_norm_parts(n) fp64 partial sums of squares, workgroup b over the
+// floats [b * grad_norm_chunk(n), (b + 1) * grad_norm_chunk(n)) of the range (workgroup 0 also takes
+// the n & 3 tail); all P partials are stored on every call, so nothing needs zeroing. The consumers
+// (clip_scale_launch, the SGD kernels' ClipArgs) sum the partials themselves (grad_clip.h).
+constexpr int kGradNormMaxParts = 1024;
+constexpr long long kGradNormMinChunk4 = 2048;  // float4 per workgroup before a second one is used
+inline int grad_norm_parts(long long n) {
+  const long long want = ((n >> 2) + kGradNormMinChunk4 - 1) / kGradNormMinChunk4;
+  int p = 1;
+  while (p < want && p < kGradNormMaxParts) p <<= 1;
+  return p;
+}
+inline long long grad_norm_chunk(long long n) {  // floats per workgroup: whole 256-thread float4 rows
+  const long long p = grad_norm_parts(n);
+  const long long c4 = (((n >> 2) + p - 1) / p + 255) / 256 * 256;
+  return (c4 > 256 ? c4 : 256) * 4;
+}
+void grad_sumsq_launch(const float* g, long long n, double* part, hipStream_t st);
+// g *= coef in place (exact zeros stay zero under a NaN coef: the arena's pad floats); stats as ClipArgs
+void clip_scale_launch(float* g, long long n, const double* part, int nparts, float max_norm, float* stats,
+                       hipStream_t st);
 // nbatches > 0: batch offset idx_off + (counter % nbatches) * B; labels_out[b] = labels[idx[...]] when given
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,

@@ -13,6 +13,7 @@
 
 #include "act_max.h"
 #include "common.h"
+#include "grad_clip.h"
 #include "kernels.h"
 #include "x3_common.h"
 
@@ -180,13 +181,40 @@ __device__ __forceinline__ void sgd_one(float& p, float g, float& b, float lr, f
   p = fmaf(d, -lr, p);
 }
 
+// Gradient-norm clip (CLIP instantiations only; ClipArgs in kernels.h): skip is workgroup-uniform. A
+// skipped step leaves p and a loaded momentum value as they are, so the stores that follow write the
+// same bits back; a skipped first momentum step stores zeros (the next, non-first step then computes
+// buf = 0 * m + d_p = d_p, the first-step rule, for dampening 0).
+template <bool CLIP>
+__device__ __forceinline__ void sgd_upd(bool skip, float& p, float g, float& b, float lr, float m, float damp, float wd,
+                                        float gs, bool nesterov, bool first, bool maximize, bool has_mom) {
+  if (CLIP && skip) {
+    if (has_mom && first) b = 0.f;
+    return;
+  }
+  sgd_one(p, g, b, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+}
+// gs *= coef and the skip decision, in the kernel's prologue (every workgroup gets the same bits);
+// workgroup 0 records norm / coef / skipped steps
+__device__ __forceinline__ bool sgd_clip_prologue(const ClipArgs& clip, float& gs) {
+  const ClipCoef c = clip_coef_block(clip.part, clip.nparts, clip.max_norm);
+  const bool skip = clip.skip_nonfinite && clip_nonfinite(c.norm);
+  if (clip.stats && blockIdx.x == 0 && threadIdx.x == 0) clip_write_stats(clip.stats, c, skip);
+  gs *= c.coef;
+  return skip;
+}
+
+template <bool CLIP>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                  long long n, const float* __restrict__ lr_ptr, float lr_host, float m,
-                                                 float damp, float wd, float gs, int flags, long long* counter) {
+                                                 float damp, float wd, float gs, int flags, long long* counter,
+                                                 ClipArgs clip) {
   const bool nesterov = flags & 1, first = flags & 2, maximize = flags & 4, has_mom = flags & 8;
   // a data loader's step counter advanced by the step (one dispatch less per step; the counter is
   // read by this step's augment kernel, which ran before)
   if (counter && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1;
+  bool skip = false;
+  if (CLIP) skip = sgd_clip_prologue(clip, gs);
   const float lr = lr_ptr ? lr_ptr[0] : lr_host;
   const long long n4 = n >> 2;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -195,10 +223,10 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     float4 pv = ld4(p + 4 * i);
     const float4 gv = ld4(g + 4 * i);
     float4 bv = has_mom && !first ? ld4(buf + 4 * i) : f4zero();
-    sgd_one(pv.x, gv.x, bv.x, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-    sgd_one(pv.y, gv.y, bv.y, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-    sgd_one(pv.z, gv.z, bv.z, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-    sgd_one(pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+    sgd_upd<CLIP>(skip, pv.x, gv.x, bv.x, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+    sgd_upd<CLIP>(skip, pv.y, gv.y, bv.y, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+    sgd_upd<CLIP>(skip, pv.z, gv.z, bv.z, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+    sgd_upd<CLIP>(skip, pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
     st4(p + 4 * i, pv);
     if (has_mom) st4(buf + 4 * i, bv);
   }
@@ -206,7 +234,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     const long long i = (n4 << 2) + threadIdx.x;
     float bb = has_mom && !first ? buf[i] : 0.f;
     float pp = p[i];
-    sgd_one(pp, g[i], has_mom ? bb : dummy, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+    sgd_upd<CLIP>(skip, pp, g[i], has_mom ? bb : dummy, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
     p[i] = pp;
     if (has_mom) buf[i] = bb;
   }
@@ -242,18 +270,21 @@ __device__ __forceinline__ void tile_max_store(const unsigned* s, float* __restr
 // sgd_one), store p / buf in place, then the |max| and the transpose of the NEW p through LDS.
 // Blocks [nblk_w, ...) each run sgd_kernel's float4 update over one chunk of the arena that no conv
 // weight covers (biases, BatchNorm parameters, the classifier).
+template <bool CLIP>
 __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ buf, const SgdPrepSeg* __restrict__ segs,
                                                       int nseg, int nblk_w, const SgdPrepChunk* __restrict__ chunks,
                                                       float* __restrict__ part, const float* __restrict__ lr_ptr,
                                                       float lr_host, float m, float damp, float wd, float gs,
-                                                      int flags, long long* counter) {
+                                                      int flags, long long* counter, ClipArgs clip) {
   // taps per group: 3 x 3 float4 in flight per thread keeps the kernel near 64 VGPRs (8 waves per
   // SIMD for this bandwidth-bound pass; a whole 3x3 filter per group held 256 VGPRs, 1 wave per SIMD)
   constexpr int TG = 3;
   if (counter && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1;  // as sgd_kernel
   __shared__ float tile[TG][32][33];
   __shared__ unsigned smax[64];
+  bool skip = false;
+  if (CLIP) skip = sgd_clip_prologue(clip, gs);  // as sgd_kernel; the |max| / W^T below are of the unchanged p
   const bool nesterov = flags & 1, first = flags & 2, maximize = flags & 4, has_mom = flags & 8;
   const float lr = lr_ptr ? lr_ptr[0] : lr_host;
   const int b = blockIdx.x;
@@ -264,10 +295,10 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
       float4 pv = ld4(p + e);
       const float4 gv = ld4(g + e);
       float4 bv = has_mom && !first ? ld4(buf + e) : f4zero();
-      sgd_one(pv.x, gv.x, bv.x, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-      sgd_one(pv.y, gv.y, bv.y, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-      sgd_one(pv.z, gv.z, bv.z, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-      sgd_one(pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      sgd_upd<CLIP>(skip, pv.x, gv.x, bv.x, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      sgd_upd<CLIP>(skip, pv.y, gv.y, bv.y, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      sgd_upd<CLIP>(skip, pv.z, gv.z, bv.z, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      sgd_upd<CLIP>(skip, pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
       st4(p + e, pv);
       if (has_mom) st4(buf + e, bv);
     }
@@ -309,10 +340,10 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
       }
 #pragma unroll
       for (int q = 0; q < TG; ++q) {
-        sgd_one(vp[q].x, vg[q].x, vb[q].x, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-        sgd_one(vp[q].y, vg[q].y, vb[q].y, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-        sgd_one(vp[q].z, vg[q].z, vb[q].z, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
-        sgd_one(vp[q].w, vg[q].w, vb[q].w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+        sgd_upd<CLIP>(skip, vp[q].x, vg[q].x, vb[q].x, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+        sgd_upd<CLIP>(skip, vp[q].y, vg[q].y, vb[q].y, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+        sgd_upd<CLIP>(skip, vp[q].z, vg[q].z, vb[q].z, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+        sgd_upd<CLIP>(skip, vp[q].w, vg[q].w, vb[q].w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
         if (off[q] != kOOB) {
           st4(pw + (off[q] >> 2), vp[q]);
           if (has_mom) st4(bw + (off[q] >> 2), vb[q]);
@@ -376,7 +407,7 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
       for (int q = 0; q < TG; ++q)
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-          sgd_one(vp[q][jj], vg[q][jj], vb[q][jj], lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+          sgd_upd<CLIP>(skip, vp[q][jj], vg[q][jj], vb[q][jj], lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
           if (off[q][jj] != kOOB) {
             pw[off[q][jj] >> 2] = vp[q][jj];
             if (has_mom) bw[off[q][jj] >> 2] = vb[q][jj];
@@ -991,19 +1022,27 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
 }
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
-                hipStream_t st, long long* counter) {
+                hipStream_t st, long long* counter, const ClipArgs& clip) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr, momentum,
-                     dampening, wd, grad_scale, flags, counter);
+  if (clip.part)
+    hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
+                       momentum, dampening, wd, grad_scale, flags, counter, clip);
+  else
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
+                       momentum, dampening, wd, grad_scale, flags, counter, clip);
 }
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
-                     bool maximize, hipStream_t st, long long* counter) {
+                     bool maximize, hipStream_t st, long long* counter, const ClipArgs& clip) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
   if (nblk_w + nchunk <= 0) return;
-  hipLaunchKernelGGL(sgd_prep_kernel, dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, nseg, nblk_w, chunks,
-                     wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter);
+  if (clip.part)
+    hipLaunchKernelGGL(sgd_prep_kernel<true>, dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, nseg, nblk_w,
+                       chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter, clip);
+  else
+    hipLaunchKernelGGL(sgd_prep_kernel<false>, dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, nseg, nblk_w,
+                       chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter, clip);
 }
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,

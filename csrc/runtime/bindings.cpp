@@ -95,14 +95,22 @@ PYBIND11_MODULE(_C, m) {
         "that produced the Linear's input, link_*): {dlogits, dx, dw, db, part}");
   m.def("sgd_step", &sgd_step, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr_t"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("grad_scale"), py::arg("nesterov"),
-        py::arg("first"), py::arg("maximize"), py::arg("counter") = py::none());
+        py::arg("first"), py::arg("maximize"), py::arg("counter") = py::none(), py::arg("clip_part") = py::none(),
+        py::arg("max_norm") = 0.0, py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false);
+  m.def("grad_norm_parts", &grad_norm_parts_, py::arg("n"), "partials grad_sumsq writes for a range of n floats");
+  m.def("grad_norm_chunk", &grad_norm_chunk_, py::arg("n"), "floats of the range each grad_sumsq workgroup owns");
+  m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("part"),
+        "fp64 partial sums of squares of a flat fp32 range (all grad_norm_parts(n) partials are written)");
+  m.def("clip_scale", &clip_scale, py::arg("g"), py::arg("part"), py::arg("max_norm"), py::arg("stats") = py::none(),
+        "g *= min(max_norm / (norm + 1e-6), 1) in place from grad_sumsq's partials; stats[0..1] = norm, coef");
   m.def("sgd_prep_plan", &sgd_prep_plan, py::arg("flat"), py::arg("start"), py::arg("end"), py::arg("weights"),
         py::arg("want_t"), py::arg("amax_out") = py::none(), py::arg("amax_offsets") = std::vector<int64_t>{},
         "plan of the fused SGD + weight-preparation step over an arena range");
   m.def("sgd_step_prep", &sgd_step_prep, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr_t"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("grad_scale"), py::arg("nesterov"),
         py::arg("first"), py::arg("maximize"), py::arg("desc"), py::arg("meta"), py::arg("amax"),
-        py::arg("counter") = py::none(),
+        py::arg("counter") = py::none(), py::arg("clip_part") = py::none(), py::arg("max_norm") = 0.0,
+        py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false,
         "SGD over an arena range that also emits the next step's weight |max| / W^T");
   m.def("augment", &augment, py::arg("images"), py::arg("indices"), py::arg("idx_offset"), py::arg("batch"),
         py::arg("mean"), py::arg("std"), py::arg("pad"), py::arg("flip"), py::arg("counter"), py::arg("seed"),

@@ -1889,9 +1889,78 @@ long long* counter_ptr(const c10::optional<at::Tensor>& c) {
   return reinterpret_cast<long long*>(c->data_ptr<int64_t>());
 }
 
+// ---------------------------------------------------------------- gradient-norm clipping
+namespace {
+bool aligned16(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
+void check_flat_grad(const at::Tensor& g, const char* what) {
+  check_f32_cuda(g, what);
+  TORCH_CHECK(g.dim() == 1 && g.is_contiguous() && aligned16(g), what, ": flat contiguous 16-byte aligned fp32 required");
+}
+void check_partials(const at::Tensor& part, int64_t need, const at::Tensor& like) {
+  TORCH_CHECK(part.is_cuda() && part.device() == like.device() && part.scalar_type() == at::kDouble &&
+                  part.is_contiguous() && part.numel() >= need && need >= 1,
+              "clip partials must be a contiguous float64 tensor on the gradients' device holding ", need, " values");
+}
+float* stats_ptr(const c10::optional<at::Tensor>& stats, const at::Tensor& like) {
+  if (!(stats.has_value() && stats->defined())) return nullptr;
+  TORCH_CHECK(stats->is_cuda() && stats->device() == like.device() && stats->scalar_type() == at::kFloat &&
+                  stats->is_contiguous() && stats->numel() >= 3,
+              "clip stats must be a contiguous float32 tensor of at least 3 on the gradients' device");
+  return stats->data_ptr<float>();
+}
+// the clip block of a fused SGD launch: clip_part holds the partials grad_sumsq wrote for the WHOLE
+// model's gradients (all clip_part.numel() of them are summed)
+ClipArgs clip_args(const c10::optional<at::Tensor>& clip_part, double max_norm, const c10::optional<at::Tensor>& stats,
+                   bool skip_nonfinite, const at::Tensor& like) {
+  ClipArgs c;
+  if (!(clip_part.has_value() && clip_part->defined())) {
+    TORCH_CHECK(!skip_nonfinite && !(stats.has_value() && stats->defined()),
+                "sgd: stats / skip_nonfinite need the clip partials");
+    return c;
+  }
+  check_partials(*clip_part, clip_part->numel(), like);
+  TORCH_CHECK(clip_part->numel() <= kGradNormMaxParts, "sgd: at most ", kGradNormMaxParts, " clip partials");
+  TORCH_CHECK(!(max_norm < 0.0), "sgd: max_norm must not be negative");
+  c.part = clip_part->data_ptr<double>();
+  c.nparts = (int)clip_part->numel();
+  c.max_norm = (float)max_norm;
+  c.stats = stats_ptr(stats, like);
+  c.skip_nonfinite = skip_nonfinite ? 1 : 0;
+  return c;
+}
+}  // namespace
+
+int64_t grad_norm_parts_(int64_t n) {
+  TORCH_CHECK(n >= 0, "grad_norm_parts: negative size");
+  return grad_norm_parts(n);
+}
+int64_t grad_norm_chunk_(int64_t n) {
+  TORCH_CHECK(n >= 0, "grad_norm_chunk: negative size");
+  return grad_norm_chunk(n);
+}
+
+void grad_sumsq(const at::Tensor& g, at::Tensor part) {
+  check_flat_grad(g, "grad_sumsq");
+  TORCH_CHECK(g.numel() >= 1, "grad_sumsq: empty range");
+  check_partials(part, grad_norm_parts(g.numel()), g);
+  grad_sumsq_launch(g.data_ptr<float>(), g.numel(), part.data_ptr<double>(), cur_stream());
+}
+
+void clip_scale(at::Tensor g, const at::Tensor& part, double max_norm, const c10::optional<at::Tensor>& stats) {
+  check_flat_grad(g, "clip_scale");
+  check_partials(part, part.numel(), g);
+  TORCH_CHECK(part.numel() <= kGradNormMaxParts, "clip_scale: at most ", kGradNormMaxParts, " partials");
+  TORCH_CHECK(!(max_norm < 0.0), "clip_scale: max_norm must not be negative");
+  if (g.numel() == 0) return;
+  clip_scale_launch(g.data_ptr<float>(), g.numel(), part.data_ptr<double>(), (int)part.numel(), (float)max_norm,
+                    stats_ptr(stats, g), cur_stream());
+}
+
 void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
-              bool maximize, const c10::optional<at::Tensor>& counter) {
+              bool maximize, const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
+              double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite) {
+  const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
   float* bp = nullptr;
@@ -1901,7 +1970,7 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
   }
   sgd_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, p.numel(), fptr(lr_t), (float)lr, (float)momentum,
              (float)dampening, (float)wd, (float)grad_scale, nesterov, first, maximize, cur_stream(),
-             counter_ptr(counter));
+             counter_ptr(counter), clip);
 }
 
 // ---------------------------------------------------------------- SGD + next-step weight preparation
@@ -1982,7 +2051,9 @@ std::vector<at::Tensor> sgd_prep_plan(const at::Tensor& flat, int64_t s, int64_t
 void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
                    double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
                    bool maximize, const at::Tensor& desc, const at::Tensor& meta, at::Tensor amax,
-                   const c10::optional<at::Tensor>& counter) {
+                   const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
+                   double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite) {
+  const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
   float* bp = nullptr;
@@ -1999,7 +2070,7 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
   sgd_prep_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, reinterpret_cast<const SgdPrepSeg*>(d), nseg, nblk,
                   reinterpret_cast<const SgdPrepChunk*>(d + nseg * sizeof(SgdPrepSeg)), nchunk,
                   amax.data_ptr<float>(), fptr(lr_t), (float)lr, (float)momentum, (float)dampening, (float)wd,
-                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter));
+                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter), clip);
 }
 
 // ---------------------------------------------------------------- data augmentation

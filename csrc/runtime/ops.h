@@ -86,10 +86,20 @@ std::vector<at::Tensor> sgd_prep_plan(const at::Tensor& flat, int64_t s, int64_t
 void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
                    double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
                    bool maximize, const at::Tensor& desc, const at::Tensor& meta, at::Tensor amax,
-                   const c10::optional<at::Tensor>& counter);
+                   const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part = c10::nullopt,
+                   double max_norm = 0.0, const c10::optional<at::Tensor>& stats = c10::nullopt,
+                   bool skip_nonfinite = false);
 void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
-              bool maximize, const c10::optional<at::Tensor>& counter);
+              bool maximize, const c10::optional<at::Tensor>& counter,
+              const c10::optional<at::Tensor>& clip_part = c10::nullopt, double max_norm = 0.0,
+              const c10::optional<at::Tensor>& stats = c10::nullopt, bool skip_nonfinite = false);
+// gradient-norm clipping over a flat fp32 range (csrc/kernels/grad_norm.hip): part[0 .. grad_norm_parts(n))
+// fp64 partial sums of squares; clip_scale: g *= min(max_norm / (norm + 1e-6), 1), stats = {norm, coef, -}
+int64_t grad_norm_parts_(int64_t n);
+int64_t grad_norm_chunk_(int64_t n);
+void grad_sumsq(const at::Tensor& g, at::Tensor part);
+void clip_scale(at::Tensor g, const at::Tensor& part, double max_norm, const c10::optional<at::Tensor>& stats);
 at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& indices, int64_t idx_offset, int64_t batch,
                    std::vector<double> mean, std::vector<double> std_, int64_t pad, bool flip,
                    const c10::optional<at::Tensor>& counter, int64_t seed, c10::optional<at::Tensor> out,
