@@ -22,6 +22,9 @@ clips with the norm of each replay. Unlike ``torch.nn.utils.clip_grad_norm_``, t
 paths (CPU, ``force_reference``, per-parameter launches) scale it in place as torch does. With
 ``skip_nonfinite`` a step whose norm is inf / NaN leaves parameters and momentum bitwise unchanged
 (counted in ``skipped_steps``); :func:`clip_grad_norm_` is the stand-alone, in-place form.
+
+:class:`LARS` is the same step with a per-parameter trust ratio (layer-wise adaptive rate scaling, for
+large global batches), derived on the device in the same way from per-parameter sums of squares.
 """
 from __future__ import annotations
 
@@ -61,6 +64,7 @@ class SGD(Optimizer):
             lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
             maximize=maximize, foreach=None, differentiable=False, fused=None,
         )
+        defaults.update(getattr(self, "_extra_defaults", {}))  # a subclass's own param_group entries (LARS)
         super().__init__(params, defaults)
         # callables run at the end of every step (DistributedDataParallel.early_buffer_broadcast
         # joins its end-of-backward buffer broadcast here, after the SGD it overlaps)
@@ -117,10 +121,14 @@ class SGD(Optimizer):
         return self._clip_stats[2] if self._clip_stats is not None else None
 
     def _clip_fusable(self) -> bool:
+        """Whether the clip can ride in this step's flat launch (see :meth:`_flat_fusable`)."""
+        return self._clip_part is not None and self._flat_fusable()
+
+    def _flat_fusable(self) -> bool:
         """Whether this step runs as one flat launch (or the split plan's launches) over one arena
-        range, so the clip can ride in it: one param group, all of its parameters with gradients, one
-        contiguous arena run, momentum buffers all first or all later."""
-        if self._arena is None or self._clip_part is None or len(self.param_groups) != 1 or _native.force_reference():
+        range, so a whole-model quantity can ride in it: one param group, all of its parameters with
+        gradients, one contiguous arena run, momentum buffers all first or all later."""
+        if self._arena is None or len(self.param_groups) != 1 or _native.force_reference():
             return False
         group = self.param_groups[0]
         params = group["params"]
@@ -244,6 +252,7 @@ class SGD(Optimizer):
             if not self._clip_fused:
                 with_grad = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
                 skip = bool(with_grad) and self._clip_reference(with_grad)
+        self._begin_step()
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
             if not params or skip:
@@ -264,6 +273,15 @@ class SGD(Optimizer):
         self._steps += 1
         self._run_post_step_joins()
         return loss
+
+    def _begin_step(self):
+        """Per-step planning of a subclass, after the clip's and before the first group's launch."""
+
+    def _flat_step_extra(self, C, arena, s, e, plan) -> dict:
+        """Further launches before, and keyword arguments of, the flat step's kernel (LARS)."""
+        return {}
+
+    _prep_cut = False  # whether the weight-preparation plan's rest chunks are cut at parameter boundaries
 
     def add_post_step_join(self, fn):
         """Run ``fn()`` at the end of every ``step()`` (e.g. to order the current stream after
@@ -424,7 +442,7 @@ class SGD(Optimizer):
     def _flat_step(self, C, arena, s, e, mom, lr_t, lr, m, damp, wd, nest, first, maxim):
         """One launch over the arena range: plain SGD, or SGD that also writes the next forward's
         weight |max| partials and W^T (FlatArena.prep_plan_for) when a model registered them."""
-        plan = arena.prep_plan_for(s, e) if self.fused_prep else None
+        plan = arena.prep_plan_for(s, e, cut=self._prep_cut) if self.fused_prep else None
         ctr, self._counter_pending = self._counter_pending, None
         clip = {}
         if self._clip_fused:
@@ -435,6 +453,7 @@ class SGD(Optimizer):
             C.grad_sumsq(arena.grad[s:e], part)
             clip = dict(clip_part=part, max_norm=self.max_grad_norm if self.max_grad_norm is not None else float("inf"),
                         stats=self._clip_stats, skip_nonfinite=self.skip_nonfinite)
+        clip.update(self._flat_step_extra(C, arena, s, e, plan))
         if plan is None:
             C.sgd_step(arena.data[s:e], arena.grad[s:e], mom, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, ctr,
                        **clip)
@@ -458,21 +477,179 @@ class SGD(Optimizer):
         arena.prep_mark_valid()
 
     def _step_reference(self, group, params):
-        lr, m, damp, wd = group["lr"], group["momentum"], group["dampening"], group["weight_decay"]
+        wd = group["weight_decay"]
         for p in params:
             d_p = p.grad if not group["maximize"] else -p.grad
             if wd != 0:
                 d_p = d_p.add(p, alpha=wd)
-            if m != 0:
-                st = self.state[p]
-                buf = st.get("momentum_buffer")
-                if buf is None:
-                    buf = torch.clone(d_p).detach()
-                    st["momentum_buffer"] = buf
-                else:
-                    buf.mul_(m).add_(d_p, alpha=1 - damp)
-                d_p = d_p.add(buf, alpha=m) if group["nesterov"] else buf
-            p.add_(d_p, alpha=-lr)
+            self._apply_reference(group, p, d_p)
+
+    def _apply_reference(self, group, p, d_p):
+        """Momentum, dampening, Nesterov and ``p -= lr * d_p`` for one parameter, with torch ops."""
+        lr, m, damp = group["lr"], group["momentum"], group["dampening"]
+        if m != 0:
+            st = self.state[p]
+            buf = st.get("momentum_buffer")
+            if buf is None:
+                buf = torch.clone(d_p).detach()
+                st["momentum_buffer"] = buf
+            else:
+                buf.mul_(m).add_(d_p, alpha=1 - damp)
+            d_p = d_p.add(buf, alpha=m) if group["nesterov"] else buf
+        p.add_(d_p, alpha=-lr)
+
+
+class LARS(SGD):
+    """:class:`SGD` with layer-wise adaptive rate scaling (You, Gitman, Ginsburg, "Large Batch Training
+    of Convolutional Networks"): every adapted parameter tensor ``w`` with scaled gradient
+    ``g^ = grad_scale * clip_coef * g`` is stepped with ``q * (g^ + wd * w)`` in place of
+    ``g^ + wd * w``, where
+
+        ``q = trust_coefficient * |w| / (|g^| + wd * |w| + eps)``  (1 when ``|w|`` or ``|g^|`` is 0)
+
+    is evaluated in fp64 from fp64 sums of squares and rounded once to fp32. A parameter is adapted
+    and decayed when ``w.ndim > 1`` or ``exclude_bias_and_norm`` is false; with the default exclusion
+    biases and BatchNorm weights get ``q = 1`` and no weight decay (the usual recipe), so the whole
+    model stays one param group and one flat launch. Momentum, dampening, Nesterov, ``maximize``,
+    ``max_grad_norm`` / ``skip_nonfinite`` and the device-side learning rate (warm-up through
+    ``lr_tensor``) are :class:`SGD`'s. ``trust_coefficient``, ``eps`` and ``exclude_bias_and_norm``
+    are ``param_groups`` entries. The defaults 0.001 and 1e-8 are the conventional ones of the paper
+    and common implementations; nothing was measured to choose them.
+
+    MI355X path, where the step is one flat launch over an arena range (the conditions of the fused
+    clip): one extra dispatch writes per-parameter fp64 partial sums of squares of weights and
+    gradients (``csrc/kernels/lars.hip``), and every workgroup of the SGD kernel, which then owns
+    elements of exactly one parameter, derives that parameter's ``q`` from them in its prologue: no
+    host sync, no atomics, so a captured hipGraph step adapts with each replay's own norms. Every
+    other case (CPU, ``force_reference``, several groups, parameters outside the arena) evaluates the
+    same formula per parameter with torch ops. ``bucket_steps`` declines, so under
+    ``DistributedDataParallel.overlap_optimizer`` the step runs whole at ``step()``.
+    """
+
+    def __init__(
+        self,
+        params,
+        lr: float,
+        momentum: float = 0.0,
+        dampening: float = 0.0,
+        weight_decay: float = 0.0,
+        nesterov: bool = False,
+        *,
+        trust_coefficient: float = 0.001,
+        eps: float = 1e-8,
+        exclude_bias_and_norm: bool = True,
+        maximize: bool = False,
+        flat: bool = True,
+        max_grad_norm: float | None = None,
+        skip_nonfinite: bool = False,
+    ):
+        if not float(trust_coefficient) >= 0.0:
+            raise ValueError(f"Invalid trust_coefficient: {trust_coefficient}")
+        if not float(eps) >= 0.0:
+            raise ValueError(f"Invalid eps: {eps}")
+        self._extra_defaults = dict(trust_coefficient=float(trust_coefficient), eps=float(eps),
+                                    exclude_bias_and_norm=bool(exclude_bias_and_norm))
+        super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, maximize=maximize, flat=flat,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        all_params = [p for g in self.param_groups for p in g["params"]]
+        self._slot = {id(p): k for k, p in enumerate(all_params)}
+        # allocated here, never inside a capture
+        self._trust = torch.ones(len(all_params), dtype=torch.float32, device=all_params[0].device)
+        self._lars_fused = False
+        self._lars_plan = None  # (key, plan) of the norms pass, per arena layout and form of the step
+
+    _prep_cut = True
+
+    @property
+    def trust_ratios(self) -> torch.Tensor:
+        """``q`` of every parameter at the last step, in ``param_groups`` order (1.0 for excluded
+        parameters): a device tensor the step writes; reading it here never syncs."""
+        return self._trust
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if hasattr(self, "_trust"):  # not the constructor's own calls
+            all_params = [p for g in self.param_groups for p in g["params"]]
+            self._slot = {id(p): k for k, p in enumerate(all_params)}
+            t = torch.ones(len(all_params), dtype=torch.float32, device=self._trust.device)
+            t[:self._trust.numel()] = self._trust
+            self._trust = t
+
+    def _on_relayout(self, arena):
+        super()._on_relayout(arena)
+        self._lars_plan = None  # offsets moved: the work list is stale
+
+    def bucket_steps(self, ranges, reducer):
+        """None: the per-bucket split of an overlapped step is not offered (the norms are local to a
+        parameter, so it is possible; until then the step runs whole at ``step()``)."""
+        return None
+
+    def _begin_step(self):
+        self._lars_fused = self._flat_fusable()
+        if self._lars_fused and self._clip_enabled and not self._clip_fused:
+            self._lars_fused = False  # the clip already scaled the gradients with torch ops
+
+    def _step_native(self, gi, group, params):
+        if not self._lars_fused:
+            return self._step_reference(group, params)  # the per-parameter launches know no trust ratio
+        done = self._steps_flat
+        super()._step_native(gi, group, params)
+        if self._steps_flat == done:
+            raise RuntimeError("LARS was planned into a flat step that did not run")
+
+    _steps_flat = 0
+
+    def _flat_step_extra(self, C, arena, s, e, plan):
+        self._steps_flat += 1
+        if not self._lars_fused:
+            return {}
+        if plan is not None and "subs" in plan:
+            raise RuntimeError("LARS cannot run over the split plan of an overlapped step")
+        group = self.param_groups[0]
+        lp = self._lars_plan_for(C, arena, s, e, plan)
+        # one extra dispatch: {sum w^2, sum g^2} of every (parameter, chunk); the workgroups of the
+        # step below add their own parameter's pairs in their prologue
+        C.lars_norms(arena.data[s:e], arena.grad[s:e], lp["desc"], lp["meta"], lp["part"])
+        return dict(lars=C.LarsStep(desc=lp["desc"], meta=lp["meta"], part=lp["part"], ratios=self._trust,
+                                    trust_coefficient=group["trust_coefficient"], eps=group["eps"],
+                                    exclude=group["exclude_bias_and_norm"]))
+
+    def _lars_plan_for(self, C, arena, s, e, plan):
+        """The norms work list over [s, e), with the owners of the weight-preparation plan's
+        workgroups when the step runs in that form. Built once per arena layout (and form), outside
+        any capture, like the weight-preparation plan itself."""
+        key = (arena.layout_gen, s, e, id(plan["desc"]) if plan is not None else None)
+        if self._lars_plan is not None and self._lars_plan[0] == key:
+            return self._lars_plan[1]
+        idx = [i for i, off in enumerate(arena.offsets) if s <= off < e]
+        ps = [arena.params[i] for i in idx]
+        r = C.lars_plan(arena.data, s, e, [arena.offsets[i] for i in idx], [arena.numels[i] for i in idx],
+                        [p.dim() for p in ps], [self._slot[id(p)] for p in ps],
+                        plan["desc"] if plan is not None else None, plan["meta"] if plan is not None else None)
+        lp = {"desc": r[0], "meta": r[1], "part": r[2], "prep_desc": plan["desc"] if plan is not None else None}
+        self._lars_plan = (key, lp)
+        return lp
+
+    def _step_reference(self, group, params):
+        wd, eta, eps = group["weight_decay"], group["trust_coefficient"], group["eps"]
+        for p in params:
+            g = p.grad
+            k = self._slot[id(p)]
+            if p.dim() > 1 or not group["exclude_bias_and_norm"]:
+                wn = p.detach().double().square().sum().sqrt()
+                gn = g.double().square().sum().sqrt()
+                q = eta * wn / (gn + wd * wn + eps)
+                q = torch.where((wn == 0) | (gn == 0), torch.ones_like(q), q).float()
+                self._trust[k].copy_(q)
+                d_p = g * q  # gs_eff = q: the reference paths scale p.grad itself by grad_scale * coef
+                if group["maximize"]:
+                    d_p = -d_p
+                if wd != 0:
+                    d_p = torch.addcmul(d_p, p, q * wd)
+            else:
+                self._trust[k].fill_(1.0)
+                d_p = g if not group["maximize"] else -g
+            self._apply_reference(group, p, d_p)
 
 
 @torch.no_grad()

@@ -30,7 +30,7 @@ from . import distributed as dist
 from .data import DeviceLoader, DistributedSampler, cifar10_binary, synthetic_cifar10, synthetic_imagenet
 from .models import get_model
 from .ops import CrossEntropyLoss, count_correct
-from .optim import SGD
+from .optim import LARS, SGD
 from .parallel import (
     BucketedOverlap,
     DistributedDataParallel,
@@ -97,6 +97,13 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 print("[cdp] rank {}: grad norm in iter {} is {} (clip coef {}, skipped steps {})".format(
                     rank, iter_number, float(optimizer.grad_norm), float(optimizer.clip_coef),
                     int(optimizer.skipped_steps)), file=sys.stderr)
+            if getattr(optimizer, "trust_ratios", None) is not None:
+                # LARS: the spread of the window's last trust ratios (stderr, as the clip line)
+                import sys
+
+                tr = optimizer.trust_ratios
+                print("[cdp] rank {}: trust ratio in iter {} is min {} max {}".format(
+                    rank, iter_number, float(tr.min()), float(tr.max())), file=sys.stderr)
         if max_iters is not None and iter_number >= max_iters:
             break
         iter_number += 1
@@ -163,8 +170,13 @@ def run(rank, size, epochs, batch_size, args):
         model = DistributedDataParallel(model, bucket_cap_mb=args.bucket_cap_mb)
     elif strategy == "bucketed_overlap":
         sync = BucketedOverlap(model, bucket_cap_mb=args.bucket_cap_mb)
-    optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
-                    max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+    if args.optimizer == "lars":
+        optimizer = LARS(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
+                         trust_coefficient=args.trust_coefficient, max_grad_norm=args.clip_grad_norm,
+                         skip_nonfinite=args.skip_nonfinite)
+    else:
+        optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
+                        max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
 
     start_epoch = 0
     if args.resume and args.checkpoint_dir:
@@ -263,6 +275,10 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=256, help="global batch (split int(B/W) per rank)")
     p.add_argument("--lr", type=float, default=0.1)
     p.add_argument("--iters", type=int, default=None, help="max iterations per epoch")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                   help="sgd (the reference's) or lars: SGD with layer-wise adaptive rate scaling, for large batches")
+    p.add_argument("--trust-coefficient", type=float, default=0.001, metavar="FLOAT",
+                   help="LARS trust coefficient (--optimizer lars)")
     p.add_argument("--clip-grad-norm", type=float, default=None, metavar="FLOAT",
                    help="clip the global gradient 2-norm to this value inside the fused optimizer step")
     p.add_argument("--skip-nonfinite", action="store_true",

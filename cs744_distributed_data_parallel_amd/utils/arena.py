@@ -219,14 +219,18 @@ class FlatArena:
         plan = self._prep_plan[1]
         return plan["amax_views"], plan["wts"]
 
-    def prep_plan_for(self, start: int, end: int):
-        """The fused-step plan for the flat range [start, end) if the registered request lies in it."""
+    def prep_plan_for(self, start: int, end: int, cut: bool = False):
+        """The fused-step plan for the flat range [start, end) if the registered request lies in it.
+
+        ``cut``: the chunks over everything but the prepared weights end at parameter boundaries, so
+        each workgroup of the step owns elements of one parameter (LARS). A cut plan also serves a
+        caller that does not ask for one."""
         req = self.prep_request
         if req is None:
             return None
         weights, want = req
         key = self._prep_key(weights, want)
-        if self._prep_plan is not None and self._prep_plan[0] == key:
+        if self._prep_plan is not None and self._prep_plan[0] == key and (self._prep_plan[1].get("cut") or not cut):
             rng = self._prep_plan[2]
             if rng == (start, end):
                 return self._prep_plan[1]
@@ -241,7 +245,8 @@ class FlatArena:
             return None
         from .. import _native
 
-        r = _native.lib().sgd_prep_plan(self.data, start, end, [w.data for w in weights], list(want))
+        cuts = [o for o in self.offsets if start < o < end] if cut else []
+        r = _native.lib().sgd_prep_plan(self.data, start, end, [w.data for w in weights], list(want), None, [], cuts)
         desc, meta, amax, wts = r[0], r[1], r[2], list(r[3:])
         # each weight's maxima: per-co partials [ceil(Ci/32), Co] then per-ci [ceil(Co/32), Ci]
         # (csrc weight_max_elems), back to back in plan order
@@ -251,7 +256,7 @@ class FlatArena:
             views.append(amax.narrow(0, b0, n))
             b0 += n
         plan = {"desc": desc, "meta": meta, "amax": amax, "amax_views": views,
-                "wts": [t if f else None for t, f in zip(wts, want)], "weights": list(weights)}
+                "wts": [t if f else None for t, f in zip(wts, want)], "weights": list(weights), "cut": bool(cut)}
         self._prep_plan = (key, plan, (start, end))
         return plan
 

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lars.h"
+
 namespace cdp {
 
 // Exact division by a runtime-invariant divisor for dividends in [0, 2^31):
@@ -175,7 +177,8 @@ struct ClipArgs {
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
-                     bool maximize, hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{});
+                     bool maximize, hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{},
+                     const LarsArgs& lars = LarsArgs{});
 void slab_sum_launch(const float* slab, int S, long long n, float* dst, bool accumulate, hipStream_t st);
 void slab_sum_strided_launch(const float* slab, int S, long long n_src, int src_cols, int dst_cols, float* dst,
                              bool accumulate, hipStream_t st);
@@ -273,7 +276,8 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
 // counter (optional): a step counter the kernel advances by one (DeviceLoader.advance_with)
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
-                hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{});
+                hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{},
+                const LarsArgs& lars = LarsArgs{});
 
 // grad_norm.hip: the global gradient norm of a flat fp32 range, in two deterministic stages.
 // grad_sumsq_launch writes P = grad_norm_parts(n) fp64 partial sums of squares, workgroup b over the

@@ -14,6 +14,7 @@
 #include "act_max.h"
 #include "common.h"
 #include "grad_clip.h"
+#include "lars.h"
 #include "kernels.h"
 #include "x3_common.h"
 
@@ -204,11 +205,23 @@ __device__ __forceinline__ bool sgd_clip_prologue(const ClipArgs& clip, float& g
   return skip;
 }
 
-template <bool CLIP>
+// LARS (LARS instantiations only; LarsArgs in lars.h): the workgroup's elements all belong to the
+// parameter `pr`. Its trust ratio q scales the two per-parameter values of sgd_one: gs = (gs * coef) * q
+// and wd = wd_w * q (wd_w: wd, or 0 for an excluded parameter), so d = q * (g * gs * coef + wd * p).
+// The parameter's first workgroup records q.
+__device__ __forceinline__ void sgd_lars_prologue(const LarsArgs& lars, const LarsParam& pr, bool first_wg, float& gs,
+                                                  float& wd) {
+  const float q = lars_ratio_block(lars, pr, gs);
+  if (first_wg && threadIdx.x == 0) lars.ratios[pr.slot] = q;
+  gs *= q;
+  wd = (lars.exclude && !pr.matrix ? 0.f : wd) * q;
+}
+
+template <bool CLIP, bool LARS>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                  long long n, const float* __restrict__ lr_ptr, float lr_host, float m,
                                                  float damp, float wd, float gs, int flags, long long* counter,
-                                                 ClipArgs clip) {
+                                                 ClipArgs clip, LarsArgs lars) {
   const bool nesterov = flags & 1, first = flags & 2, maximize = flags & 4, has_mom = flags & 8;
   // a data loader's step counter advanced by the step (one dispatch less per step; the counter is
   // read by this step's augment kernel, which ran before)
@@ -216,6 +229,26 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   bool skip = false;
   if (CLIP) skip = sgd_clip_prologue(clip, gs);
   const float lr = lr_ptr ? lr_ptr[0] : lr_host;
+  if (LARS) {
+    // one workgroup per (parameter, chunk) item of the norms pass's work list: whole float4s of one
+    // parameter, so the ratio is workgroup-uniform
+    const LarsItem it = lars.items[blockIdx.x];
+    const LarsParam pr = lars.params[it.param];
+    sgd_lars_prologue(lars, pr, (int)blockIdx.x == pr.part0, gs, wd);
+    for (int i = threadIdx.x; i < it.n4; i += 256) {
+      const long long e = it.start + 4LL * i;
+      float4 pv = ld4(p + e);
+      const float4 gv = ld4(g + e);
+      float4 bv = has_mom && !first ? ld4(buf + e) : f4zero();
+      sgd_upd<CLIP>(skip, pv.x, gv.x, bv.x, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      sgd_upd<CLIP>(skip, pv.y, gv.y, bv.y, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      sgd_upd<CLIP>(skip, pv.z, gv.z, bv.z, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      sgd_upd<CLIP>(skip, pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
+      st4(p + e, pv);
+      if (has_mom) st4(buf + e, bv);
+    }
+    return;
+  }
   const long long n4 = n >> 2;
   const long long stride = (long long)gridDim.x * blockDim.x;
   float dummy = 0.f;
@@ -270,13 +303,13 @@ __device__ __forceinline__ void tile_max_store(const unsigned* s, float* __restr
 // sgd_one), store p / buf in place, then the |max| and the transpose of the NEW p through LDS.
 // Blocks [nblk_w, ...) each run sgd_kernel's float4 update over one chunk of the arena that no conv
 // weight covers (biases, BatchNorm parameters, the classifier).
-template <bool CLIP>
+template <bool CLIP, bool LARS>
 __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ buf, const SgdPrepSeg* __restrict__ segs,
                                                       int nseg, int nblk_w, const SgdPrepChunk* __restrict__ chunks,
                                                       float* __restrict__ part, const float* __restrict__ lr_ptr,
                                                       float lr_host, float m, float damp, float wd, float gs,
-                                                      int flags, long long* counter, ClipArgs clip) {
+                                                      int flags, long long* counter, ClipArgs clip, LarsArgs lars) {
   // taps per group: 3 x 3 float4 in flight per thread keeps the kernel near 64 VGPRs (8 waves per
   // SIMD for this bandwidth-bound pass; a whole 3x3 filter per group held 256 VGPRs, 1 wave per SIMD)
   constexpr int TG = 3;
@@ -290,6 +323,10 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
   const int b = blockIdx.x;
   if (b >= nblk_w) {
     const SgdPrepChunk ch = chunks[b - nblk_w];
+    if (LARS) {  // the plan cut the rest chunks at parameter boundaries: one owner per chunk
+      const LarsParam pr = lars.params[lars.owner[nseg + b - nblk_w]];
+      sgd_lars_prologue(lars, pr, ch.start == pr.off, gs, wd);
+    }
     for (int i = threadIdx.x; i < ch.n4; i += 256) {
       const long long e = ch.start + 4LL * i;
       float4 pv = ld4(p + e);
@@ -307,6 +344,7 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
   int si = 0;
   while (si + 1 < nseg && segs[si + 1].blk0 <= b) ++si;
   const SgdPrepSeg sg = segs[si];
+  if (LARS) sgd_lars_prologue(lars, lars.params[lars.owner[si]], b == sg.blk0, gs, wd);  // a tile is of one weight
   const int Co = sg.co, T = sg.t, Ci = sg.ci;
   float* __restrict__ wt = sg.wt;
   const int local = b - sg.blk0;
@@ -1022,27 +1060,42 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
 }
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
-                hipStream_t st, long long* counter, const ClipArgs& clip) {
+                hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
+  if (lars.params) {  // one workgroup per item of the LARS work list, which tiles [0, n)
+    if (lars.nitems < 1) return;
+    if (clip.part)
+      hipLaunchKernelGGL((sgd_kernel<true, true>), dim3(lars.nitems), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
+                         momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
+    else
+      hipLaunchKernelGGL((sgd_kernel<false, true>), dim3(lars.nitems), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
+                         momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
+    return;
+  }
   if (clip.part)
-    hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
-                       momentum, dampening, wd, grad_scale, flags, counter, clip);
+    hipLaunchKernelGGL((sgd_kernel<true, false>), dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr,
+                       lr, momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
   else
-    hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
-                       momentum, dampening, wd, grad_scale, flags, counter, clip);
+    hipLaunchKernelGGL((sgd_kernel<false, false>), dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr,
+                       lr, momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
 }
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
-                     bool maximize, hipStream_t st, long long* counter, const ClipArgs& clip) {
+                     bool maximize, hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
   if (nblk_w + nchunk <= 0) return;
-  if (clip.part)
-    hipLaunchKernelGGL(sgd_prep_kernel<true>, dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, nseg, nblk_w,
-                       chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter, clip);
-  else
-    hipLaunchKernelGGL(sgd_prep_kernel<false>, dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, nseg, nblk_w,
-                       chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter, clip);
+#define CDP_SGD_PREP(CLIP, LARS)                                                                                      \
+  hipLaunchKernelGGL((sgd_prep_kernel<CLIP, LARS>), dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, nseg,  \
+                     nblk_w, chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter, clip, lars)
+  if (lars.params) {
+    if (clip.part) CDP_SGD_PREP(true, true);
+    else CDP_SGD_PREP(false, true);
+  } else {
+    if (clip.part) CDP_SGD_PREP(true, false);
+    else CDP_SGD_PREP(false, false);
+  }
+#undef CDP_SGD_PREP
 }
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,

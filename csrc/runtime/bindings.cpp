@@ -93,10 +93,30 @@ PYBIND11_MODULE(_C, m) {
         py::arg("link_pool") = false, py::arg("link_relu") = false, py::arg("link_ps") = 2,
         "CrossEntropy backward + narrow Linear backward in one launch (+ the BN backward partials of the block "
         "that produced the Linear's input, link_*): {dlogits, dx, dw, db, part}");
+  py::class_<LarsStep>(m, "LarsStep", "the LARS block of sgd_step / sgd_step_prep (default: off)")
+      .def(py::init([](c10::optional<at::Tensor> desc, c10::optional<at::Tensor> meta, c10::optional<at::Tensor> part,
+                       c10::optional<at::Tensor> ratios, double trust_coefficient, double eps, bool exclude) {
+             LarsStep l;
+             l.desc = desc, l.meta = meta, l.part = part, l.ratios = ratios;
+             l.trust_coefficient = trust_coefficient, l.eps = eps, l.exclude = exclude;
+             return l;
+           }),
+           py::arg("desc") = py::none(), py::arg("meta") = py::none(), py::arg("part") = py::none(),
+           py::arg("ratios") = py::none(), py::arg("trust_coefficient") = 0.0, py::arg("eps") = 0.0,
+           py::arg("exclude") = true);
+  m.def("lars_plan", &lars_plan, py::arg("flat"), py::arg("start"), py::arg("end"), py::arg("offsets"),
+        py::arg("numels"), py::arg("ndims"), py::arg("slots"), py::arg("prep_desc") = py::none(),
+        py::arg("prep_meta") = py::none(),
+        "plan of the LARS norms pass and step over an arena range: {descriptor, meta, fp64 partial pairs}");
+  m.def("lars_norms", &lars_norms, py::arg("w"), py::arg("g"), py::arg("desc"), py::arg("meta"), py::arg("part"),
+        "per-parameter fp64 partial sums of squares {w^2, g^2} of an arena range (every pair is written)");
+  m.def("lars_chunk", &lars_chunk_, py::arg("n"), "floats per norms chunk of a parameter of n floats");
+  m.def("lars_nparts", &lars_nparts_, py::arg("n"), "norms chunks of a parameter of n floats");
   m.def("sgd_step", &sgd_step, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr_t"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("grad_scale"), py::arg("nesterov"),
         py::arg("first"), py::arg("maximize"), py::arg("counter") = py::none(), py::arg("clip_part") = py::none(),
-        py::arg("max_norm") = 0.0, py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false);
+        py::arg("max_norm") = 0.0, py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false,
+        py::arg("lars") = LarsStep{});
   m.def("grad_norm_parts", &grad_norm_parts_, py::arg("n"), "partials grad_sumsq writes for a range of n floats");
   m.def("grad_norm_chunk", &grad_norm_chunk_, py::arg("n"), "floats of the range each grad_sumsq workgroup owns");
   m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("part"),
@@ -105,12 +125,13 @@ PYBIND11_MODULE(_C, m) {
         "g *= min(max_norm / (norm + 1e-6), 1) in place from grad_sumsq's partials; stats[0..1] = norm, coef");
   m.def("sgd_prep_plan", &sgd_prep_plan, py::arg("flat"), py::arg("start"), py::arg("end"), py::arg("weights"),
         py::arg("want_t"), py::arg("amax_out") = py::none(), py::arg("amax_offsets") = std::vector<int64_t>{},
+        py::arg("cuts") = std::vector<int64_t>{},
         "plan of the fused SGD + weight-preparation step over an arena range");
   m.def("sgd_step_prep", &sgd_step_prep, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr_t"), py::arg("lr"),
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("grad_scale"), py::arg("nesterov"),
         py::arg("first"), py::arg("maximize"), py::arg("desc"), py::arg("meta"), py::arg("amax"),
         py::arg("counter") = py::none(), py::arg("clip_part") = py::none(), py::arg("max_norm") = 0.0,
-        py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false,
+        py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false, py::arg("lars") = LarsStep{},
         "SGD over an arena range that also emits the next step's weight |max| / W^T");
   m.def("augment", &augment, py::arg("images"), py::arg("indices"), py::arg("idx_offset"), py::arg("batch"),
         py::arg("mean"), py::arg("std"), py::arg("pad"), py::arg("flip"), py::arg("counter"), py::arg("seed"),

@@ -1930,6 +1930,163 @@ ClipArgs clip_args(const c10::optional<at::Tensor>& clip_part, double max_norm, 
 }
 }  // namespace
 
+// ---------------------------------------------------------------- LARS
+namespace {
+size_t lars_blob_bytes(int64_t np, int64_t ni, int64_t nown) {
+  return (size_t)np * sizeof(LarsParam) + (size_t)ni * sizeof(LarsItem) + (size_t)nown * sizeof(int);
+}
+// the LARS block of a fused SGD launch; nblocks_prep: segments + rest chunks of the weight-preparation
+// plan the step runs with, -1 for the plain step
+LarsArgs lars_args(const LarsStep& ls, const at::Tensor& like, int64_t nblocks_prep) {
+  const auto &desc = ls.desc, &meta = ls.meta, &part = ls.part, &ratios = ls.ratios;
+  const double trust_coefficient = ls.trust_coefficient, eps = ls.eps;
+  LarsArgs a;
+  if (!(desc.has_value() && desc->defined())) return a;
+  TORCH_CHECK(meta.has_value() && meta->defined() && meta->device().is_cpu() && meta->scalar_type() == at::kLong &&
+                  meta->numel() == 4,
+              "lars: meta from lars_plan required");
+  const int64_t* mt = meta->data_ptr<int64_t>();
+  const int64_t np = mt[0], ni = mt[1], nown = mt[2], total = mt[3];
+  TORCH_CHECK(desc->is_cuda() && desc->device() == like.device() && desc->scalar_type() == at::kByte &&
+                  desc->is_contiguous() && desc->numel() >= (int64_t)lars_blob_bytes(np, ni, nown),
+              "lars: descriptor from lars_plan required");
+  TORCH_CHECK(like.numel() == total, "lars: the plan covers ", total, " floats, the step ", like.numel());
+  TORCH_CHECK(nblocks_prep < 0 ? nown == 0 : nown == nblocks_prep,
+              "lars: the plan was built for another form of the step (plain / weight-preparation)");
+  TORCH_CHECK(part.has_value() && part->defined() && part->is_cuda() && part->device() == like.device() &&
+                  part->scalar_type() == at::kDouble && part->is_contiguous() && part->numel() >= 2 * ni,
+              "lars: partials must be a contiguous float64 device tensor of 2 per work item");
+  TORCH_CHECK(ratios.has_value() && ratios->defined() && ratios->is_cuda() && ratios->device() == like.device() &&
+                  ratios->scalar_type() == at::kFloat && ratios->is_contiguous() && ratios->numel() >= np,
+              "lars: trust ratios must be a contiguous float32 device tensor of one per parameter");
+  TORCH_CHECK(!(trust_coefficient < 0.0) && !(eps < 0.0), "lars: trust_coefficient and eps must not be negative");
+  const uint8_t* d = desc->data_ptr<uint8_t>();
+  a.params = reinterpret_cast<const LarsParam*>(d);
+  a.items = reinterpret_cast<const LarsItem*>(d + np * sizeof(LarsParam));
+  a.owner = reinterpret_cast<const int*>(d + np * sizeof(LarsParam) + ni * sizeof(LarsItem));
+  a.part = part->data_ptr<double>();
+  a.ratios = ratios->data_ptr<float>();
+  a.eta = trust_coefficient;
+  a.eps = eps;
+  a.nitems = (int)ni;
+  a.exclude = ls.exclude ? 1 : 0;
+  return a;
+}
+}  // namespace
+
+int64_t lars_chunk_(int64_t n) {
+  TORCH_CHECK(n >= 0, "lars_chunk: negative size");
+  return 4 * lars_chunk4((n + 3) / 4);
+}
+int64_t lars_nparts_(int64_t n) {
+  TORCH_CHECK(n >= 0, "lars_nparts: negative size");
+  return lars_nparts((n + 3) / 4);
+}
+
+// Plan of the LARS norms pass and step over the flat range [s, e) of `flat`: the range's parameters
+// in arena order (offsets into flat, numels, ndims, and each one's slot in the trust-ratio tensor);
+// they must tile the range, each padded to whole float4. With the plan of a weight-preparation step
+// over the same range (prep_desc / prep_meta from sgd_prep_plan with its rest chunks cut at the
+// parameter boundaries) the owner of each of that launch's workgroups is recorded too. Returns
+// {descriptor (device bytes), meta (cpu int64: parameters, items, owners, floats), partials (device
+// fp64, 2 per item)}. Built once per arena layout, outside any capture.
+std::vector<at::Tensor> lars_plan(const at::Tensor& flat, int64_t s, int64_t e, const std::vector<int64_t>& offsets,
+                                  const std::vector<int64_t>& numels, const std::vector<int64_t>& ndims,
+                                  const std::vector<int64_t>& slots, const c10::optional<at::Tensor>& prep_desc,
+                                  const c10::optional<at::Tensor>& prep_meta) {
+  check_f32_cuda(flat, "arena");
+  const size_t np = offsets.size();
+  TORCH_CHECK(np >= 1 && numels.size() == np && ndims.size() == np && slots.size() == np,
+              "lars_plan: one offset, numel, ndim and slot per parameter");
+  TORCH_CHECK(0 <= s && s < e && e <= flat.numel() && (s % 4) == 0 && ((e - s) % 4) == 0, "lars_plan: bad range");
+  std::vector<LarsParam> ps;
+  std::vector<LarsItem> items;
+  long long cur = s;
+  for (size_t i = 0; i < np; ++i) {
+    TORCH_CHECK(offsets[i] == cur && numels[i] >= 1, "lars_plan: the parameters must tile the range in order");
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < (int64_t)np, "lars_plan: bad trust-ratio slot");
+    const long long n4 = (numels[i] + 3) / 4;
+    const int parts = lars_nparts(n4);
+    const long long c4 = lars_chunk4(n4);
+    TORCH_CHECK(items.size() + (size_t)parts < (size_t)1 << 30, "lars_plan: too many work items");
+    LarsParam p{cur - s, n4, (int)items.size(), 0, (int)slots[i], ndims[i] > 1 ? 1 : 0};
+    for (long long a = 0; a < n4; a += c4) {
+      items.push_back(LarsItem{p.off + 4 * a, (int)std::min<long long>(c4, n4 - a), (int)i});
+      ++p.nparts;
+    }
+    TORCH_CHECK(p.nparts >= 1 && p.nparts <= kLarsMaxParts, "lars_plan: partial count out of range");
+    ps.push_back(p);
+    cur += 4 * n4;
+  }
+  TORCH_CHECK(cur == e, "lars_plan: the parameters must tile the range");
+  std::vector<int> owner;
+  if (prep_desc.has_value() && prep_desc->defined()) {
+    TORCH_CHECK(prep_meta.has_value() && prep_meta->device().is_cpu() && prep_meta->numel() == 3,
+                "lars_plan: prep_meta from sgd_prep_plan required");
+    const int64_t* mt = prep_meta->data_ptr<int64_t>();
+    const int64_t nseg = mt[0], nchunk = mt[2];
+    at::Tensor host = prep_desc->to(at::kCPU).contiguous();
+    TORCH_CHECK(host.numel() >= (int64_t)(nseg * sizeof(SgdPrepSeg) + nchunk * sizeof(SgdPrepChunk)),
+                "lars_plan: descriptor smaller than the plan");
+    const SgdPrepSeg* segs = reinterpret_cast<const SgdPrepSeg*>(host.data_ptr<uint8_t>());
+    const SgdPrepChunk* chunks =
+        reinterpret_cast<const SgdPrepChunk*>(host.data_ptr<uint8_t>() + nseg * sizeof(SgdPrepSeg));
+    auto find = [&](long long off) {  // the parameter holding the float at `off`
+      size_t lo = 0, hi = np;
+      while (hi - lo > 1) {
+        const size_t mid = (lo + hi) / 2;
+        if (ps[mid].off <= off) lo = mid;
+        else hi = mid;
+      }
+      return lo;
+    };
+    for (int64_t k = 0; k < nseg; ++k) {
+      const size_t i = find(segs[k].off);
+      TORCH_CHECK(ps[i].off == segs[k].off && (long long)segs[k].co * segs[k].t * segs[k].ci <= 4 * ps[i].n4,
+                  "lars_plan: a prepared weight is not one parameter of the range");
+      owner.push_back((int)i);
+    }
+    for (int64_t k = 0; k < nchunk; ++k) {
+      const size_t i = find(chunks[k].start);
+      TORCH_CHECK(chunks[k].start >= ps[i].off && chunks[k].start + 4LL * chunks[k].n4 <= ps[i].off + 4 * ps[i].n4,
+                  "lars_plan: the weight-preparation plan is not cut at parameter boundaries");
+      owner.push_back((int)i);
+    }
+  }
+  const size_t pb = ps.size() * sizeof(LarsParam), ib = items.size() * sizeof(LarsItem), ob = owner.size() * sizeof(int);
+  at::Tensor host = at::empty({(long long)std::max<size_t>(pb + ib + ob, 16)}, at::TensorOptions().dtype(at::kByte));
+  std::memcpy(host.data_ptr<uint8_t>(), ps.data(), pb);
+  std::memcpy(host.data_ptr<uint8_t>() + pb, items.data(), ib);
+  if (ob) std::memcpy(host.data_ptr<uint8_t>() + pb + ib, owner.data(), ob);
+  at::Tensor desc = host.to(flat.device());
+  at::Tensor meta =
+      at::tensor({(int64_t)ps.size(), (int64_t)items.size(), (int64_t)owner.size(), (int64_t)(e - s)}, at::kLong);
+  at::Tensor part = at::zeros({2 * (long long)items.size()}, flat.options().dtype(at::kDouble));
+  return {desc, meta, part};
+}
+
+// the norms pass: all 2 * items partials are written
+void lars_norms(const at::Tensor& w, const at::Tensor& g, const at::Tensor& desc, const at::Tensor& meta,
+                at::Tensor part) {
+  check_flat_grad(w, "lars_norms weights");
+  check_flat_grad(g, "lars_norms gradients");
+  TORCH_CHECK(meta.device().is_cpu() && meta.scalar_type() == at::kLong && meta.numel() == 4,
+              "lars_norms: meta from lars_plan required");
+  const int64_t* mt = meta.data_ptr<int64_t>();
+  const int64_t np = mt[0], ni = mt[1];
+  TORCH_CHECK(w.numel() == mt[3] && g.numel() == mt[3] && w.device() == g.device(),
+              "lars_norms: the plan covers ", mt[3], " floats");
+  TORCH_CHECK(desc.is_cuda() && desc.device() == w.device() && desc.scalar_type() == at::kByte && desc.is_contiguous() &&
+                  desc.numel() >= (int64_t)lars_blob_bytes(np, ni, mt[2]),
+              "lars_norms: descriptor from lars_plan required");
+  TORCH_CHECK(part.is_cuda() && part.device() == w.device() && part.scalar_type() == at::kDouble &&
+                  part.is_contiguous() && part.numel() >= 2 * ni,
+              "lars_norms: partials must be a contiguous float64 device tensor of 2 per work item");
+  lars_norms_launch(w.data_ptr<float>(), g.data_ptr<float>(),
+                    reinterpret_cast<const LarsItem*>(desc.data_ptr<uint8_t>() + np * sizeof(LarsParam)), (int)ni,
+                    part.data_ptr<double>(), cur_stream());
+}
+
 int64_t grad_norm_parts_(int64_t n) {
   TORCH_CHECK(n >= 0, "grad_norm_parts: negative size");
   return grad_norm_parts(n);
@@ -1959,7 +2116,7 @@ void clip_scale(at::Tensor g, const at::Tensor& part, double max_norm, const c10
 void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
               bool maximize, const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
-              double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite) {
+              double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite, const LarsStep& lars) {
   const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
@@ -1968,9 +2125,14 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
     TORCH_CHECK(buf.has_value() && buf->numel() == p.numel(), "sgd: momentum buffer required");
     bp = buf->data_ptr<float>();
   }
+  LarsArgs la = lars_args(lars, p, -1);
+  if (la.params) {
+    la.wd = wd;
+    TORCH_CHECK(aligned16(p) && aligned16(g) && (!bp || aligned16(*buf)), "lars: 16-byte aligned tensors required");
+  }
   sgd_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, p.numel(), fptr(lr_t), (float)lr, (float)momentum,
              (float)dampening, (float)wd, (float)grad_scale, nesterov, first, maximize, cur_stream(),
-             counter_ptr(counter), clip);
+             counter_ptr(counter), clip, la);
 }
 
 // ---------------------------------------------------------------- SGD + next-step weight preparation
@@ -1983,9 +2145,10 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
 // With amax_out / amax_offsets the maxima go to caller-owned storage at the given float offsets
 // (one per weight): the per-bucket plans of an overlapped optimizer step share ONE maxima tensor,
 // laid out as the forward expects, and each writes only its own weights' part of it.
+// Without cuts the chunks are exactly those of a plan built before cuts existed.
 std::vector<at::Tensor> sgd_prep_plan(const at::Tensor& flat, int64_t s, int64_t e, const std::vector<at::Tensor>& ws,
                                       const std::vector<bool>& want_t, const c10::optional<at::Tensor>& amax_out,
-                                      const std::vector<int64_t>& amax_offsets) {
+                                      const std::vector<int64_t>& amax_offsets, const std::vector<int64_t>& cuts) {
   check_f32_cuda(flat, "arena");
   TORCH_CHECK(ws.size() == want_t.size() && !ws.empty(), "sgd_prep_plan: one want_t flag per weight");
   const bool ext = amax_out.has_value() && amax_out->defined();
@@ -2024,9 +2187,23 @@ std::vector<at::Tensor> sgd_prep_plan(const at::Tensor& flat, int64_t s, int64_t
   std::sort(covered.begin(), covered.end());
   std::vector<SgdPrepChunk> chunks;
   long long cur = 0;
+  // cuts (sorted offsets into flat, whole float4s): no rest chunk crosses one, so that each chunk lies
+  // in one parameter (the LARS step, whose workgroups each own elements of exactly one parameter)
+  std::vector<long long> cut;
+  for (int64_t c : cuts) {
+    TORCH_CHECK(c >= s && c <= e && ((c - s) % 4) == 0 && (cut.empty() || cut.back() <= c - s),
+                "sgd_prep_plan: cuts must be sorted float4 offsets inside the range");
+    cut.push_back(c - s);
+  }
   auto add_gap = [&](long long a, long long b) {
-    for (long long x = a; x < b; x += 4LL * kSgdPrepChunk4)
-      chunks.push_back(SgdPrepChunk{x, (int)(std::min<long long>(b - x, 4LL * kSgdPrepChunk4) / 4), 0});
+    long long x = a;
+    while (x < b) {
+      long long end = std::min<long long>(b, x + 4LL * kSgdPrepChunk4);
+      const auto nx = std::upper_bound(cut.begin(), cut.end(), x);
+      if (nx != cut.end() && *nx < end) end = *nx;
+      chunks.push_back(SgdPrepChunk{x, (int)((end - x) / 4), 0});
+      x = end;
+    }
   };
   for (const auto& c : covered) {
     TORCH_CHECK(c.first >= cur, "sgd_prep_plan: overlapping weights");
@@ -2052,7 +2229,8 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
                    double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
                    bool maximize, const at::Tensor& desc, const at::Tensor& meta, at::Tensor amax,
                    const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
-                   double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite) {
+                   double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite,
+                   const LarsStep& lars) {
   const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
@@ -2067,10 +2245,15 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
   TORCH_CHECK(desc.numel() >= (int64_t)(nseg * sizeof(SgdPrepSeg) + nchunk * sizeof(SgdPrepChunk)),
               "sgd_step_prep: descriptor smaller than the plan");
   const uint8_t* d = desc.data_ptr<uint8_t>();
+  LarsArgs la = lars_args(lars, p, (int64_t)nseg + nchunk);
+  if (la.params) {
+    la.wd = wd;
+    TORCH_CHECK(aligned16(p) && aligned16(g) && (!bp || aligned16(*buf)), "lars: 16-byte aligned tensors required");
+  }
   sgd_prep_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, reinterpret_cast<const SgdPrepSeg*>(d), nseg, nblk,
                   reinterpret_cast<const SgdPrepChunk*>(d + nseg * sizeof(SgdPrepSeg)), nchunk,
                   amax.data_ptr<float>(), fptr(lr_t), (float)lr, (float)momentum, (float)dampening, (float)wd,
-                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter), clip);
+                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter), clip, la);
 }
 
 // ---------------------------------------------------------------- data augmentation

@@ -79,21 +79,39 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
                                         const c10::optional<at::Tensor>& link_y = c10::nullopt,
                                         const c10::optional<at::Tensor>& link_stats = c10::nullopt,
                                         bool link_pool = false, bool link_relu = false, int64_t link_ps = 2);
+// The LARS block of a fused SGD step (csrc/kernels/lars.h): descriptor, meta and partials from
+// lars_plan, the partials filled by lars_norms just before; ratios: one float per parameter.
+// Without a descriptor the step is plain SGD.
+struct LarsStep {
+  c10::optional<at::Tensor> desc, meta, part, ratios;
+  double trust_coefficient = 0.0, eps = 0.0;
+  bool exclude = true;
+};
+std::vector<at::Tensor> lars_plan(const at::Tensor& flat, int64_t s, int64_t e, const std::vector<int64_t>& offsets,
+                                  const std::vector<int64_t>& numels, const std::vector<int64_t>& ndims,
+                                  const std::vector<int64_t>& slots,
+                                  const c10::optional<at::Tensor>& prep_desc = c10::nullopt,
+                                  const c10::optional<at::Tensor>& prep_meta = c10::nullopt);
+void lars_norms(const at::Tensor& w, const at::Tensor& g, const at::Tensor& desc, const at::Tensor& meta, at::Tensor part);
+int64_t lars_chunk_(int64_t n);   // floats per norms chunk of a parameter of n floats
+int64_t lars_nparts_(int64_t n);  // chunks (= partial pairs) of such a parameter
 std::vector<at::Tensor> sgd_prep_plan(const at::Tensor& flat, int64_t s, int64_t e, const std::vector<at::Tensor>& ws,
                                       const std::vector<bool>& want_t,
                                       const c10::optional<at::Tensor>& amax_out = c10::nullopt,
-                                      const std::vector<int64_t>& amax_offsets = {});
+                                      const std::vector<int64_t>& amax_offsets = {},
+                                      const std::vector<int64_t>& cuts = {});
 void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
                    double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
                    bool maximize, const at::Tensor& desc, const at::Tensor& meta, at::Tensor amax,
                    const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part = c10::nullopt,
                    double max_norm = 0.0, const c10::optional<at::Tensor>& stats = c10::nullopt,
-                   bool skip_nonfinite = false);
+                   bool skip_nonfinite = false, const LarsStep& lars = LarsStep{});
 void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
               bool maximize, const c10::optional<at::Tensor>& counter,
               const c10::optional<at::Tensor>& clip_part = c10::nullopt, double max_norm = 0.0,
-              const c10::optional<at::Tensor>& stats = c10::nullopt, bool skip_nonfinite = false);
+              const c10::optional<at::Tensor>& stats = c10::nullopt, bool skip_nonfinite = false,
+              const LarsStep& lars = LarsStep{});
 // gradient-norm clipping over a flat fp32 range (csrc/kernels/grad_norm.hip): part[0 .. grad_norm_parts(n))
 // fp64 partial sums of squares; clip_scale: g *= min(max_norm / (norm + 1e-6), 1), stats = {norm, coef, -}
 int64_t grad_norm_parts_(int64_t n);
