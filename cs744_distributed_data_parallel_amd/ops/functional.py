@@ -371,13 +371,14 @@ def linear(x, weight, bias=None):
 # --------------------------------------------------------------------------- cross entropy
 class _XEnt(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target):
+    def forward(ctx, logits, target, label_smoothing=0.0):
         ctx.save_for_backward(logits, target)
+        ctx.eps = float(label_smoothing)  # constant for a criterion: a host kernel argument of both passes
         # logits straight from a narrow native Linear (VGG's fc1): its backward rides on ours
         node = logits.grad_fn
         ctx.lin = node if (getattr(node, "narrow", False) and hasattr(node, "fused")
                            and logits.shape[0] * logits.shape[1] <= _XENT_LIN_MAX) else None
-        return _native.lib().xent_fwd(logits, target)
+        return _native.lib().xent_fwd(logits, target, None, ctx.eps)
 
     @staticmethod
     def backward(ctx, g):
@@ -394,32 +395,55 @@ class _XEnt(torch.autograd.Function):
             dl, dx, dw, db, part = _native.lib().xent_linear_bwd(
                 g.reshape(1), logits, target, x, w, nig[0], has_b, _slot(wp, nig[1]), _slot(bp, nig[2] and has_b),
                 li.y if link else None, li.stats if link else None, bool(li.pool) if link else False,
-                bool(li.relu) if link else False, li.ps if link else 2)
+                bool(li.relu) if link else False, li.ps if link else 2, label_smoothing=ctx.eps)
             if link:  # the producer block's backward takes these partials if its gradient is this dX
                 li.part, li.gptr, li.gver = part, dx.data_ptr(), dx._version
             lin.fused = (dl, dx if nig[0] else None, dw, db if has_b else None)
-            return dl, None
-        return _native.lib().xent_bwd(g.reshape(1), logits, target), None
+            return dl, None, None
+        return _native.lib().xent_bwd(g.reshape(1), logits, target, ctx.eps), None, None
 
 
 _XENT_LIN_MAX = 8192  # batch x classes held in each block's LDS (csrc kernels.h kXentLinMax)
 
 
-def cross_entropy(logits, target):
-    """Mean-reduced softmax cross-entropy (``torch.nn.CrossEntropyLoss()`` defaults)."""
+def cross_entropy(logits, target, label_smoothing=0.0):
+    """Mean-reduced softmax cross-entropy (``torch.nn.CrossEntropyLoss()`` defaults), optionally against
+    the smoothed target distribution ``(1 - label_smoothing) * onehot + label_smoothing / C``."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
     if use_native(logits) and logits.dim() == 2 and logits.dtype == torch.float32:
-        return _XEnt.apply(logits, target)
-    return F.cross_entropy(logits, target)
+        return _XEnt.apply(logits, target, float(label_smoothing))
+    return F.cross_entropy(logits, target, label_smoothing=label_smoothing)
 
 
-def count_correct(logits, target, out=None):
-    """Top-1 correct count (``output.max(1)`` + ``eq`` + ``sum``) as an int64 device tensor."""
+def topk_hits(logits, target, topk):
+    """Per-row top-k membership of the target by rank: ``rank = #{c : z_c > z_t, or z_c == z_t and c < t}``,
+    a hit when ``rank < topk`` (ties go to the lower index; ``torch.topk``'s tie order is unspecified).
+    Rows with a target out of range or a NaN target logit are not hits."""
+    C = logits.shape[1]
+    tok = (target >= 0) & (target < C)
+    t = target.clamp(0, C - 1).unsqueeze(1)
+    zt = logits.gather(1, t)
+    idx = torch.arange(C, device=logits.device).unsqueeze(0)
+    rank = ((logits > zt) | ((logits == zt) & (idx < t))).sum(1)
+    return tok & (zt.squeeze(1) == zt.squeeze(1)) & (rank < topk)
+
+
+def count_correct(logits, target, out=None, topk=1):
+    """Top-k correct count as an int64 device tensor. ``topk=1`` is the reference's ``output.max(1)`` +
+    ``eq`` + ``sum``; ``topk > 1`` counts the rows whose target ranks among the ``topk`` largest logits
+    (:func:`topk_hits`: ties go to the lower index)."""
+    if topk < 1:
+        raise ValueError(f"topk must be >= 1. Got: {topk}")
     if use_native(logits):
         if out is None:
             out = torch.zeros(1, dtype=torch.long, device=logits.device)
-        _native.lib().xent_fwd(logits.detach().float().contiguous(), target, out)
+        _native.lib().xent_fwd(logits.detach().float().contiguous(), target, out, 0.0, int(topk))
         return out
-    c = logits.max(1)[1].eq(target).sum().reshape(1)
+    if topk > 1:
+        c = topk_hits(logits, target, topk).sum().reshape(1)
+    else:
+        c = logits.max(1)[1].eq(target).sum().reshape(1)
     if out is None:
         return c
     out += c

@@ -110,16 +110,21 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
     return iter_number
 
 
-def test_model(model, test_loader, criterion, print_fn=print):
+def test_model(model, test_loader, criterion, print_fn=print, topk=None):
+    """The reference's eval loop; ``topk`` (``--eval-topk K``) also counts top-K hits in a second device
+    counter and prints them to stderr (stdout keeps the reference's line)."""
     model.eval()
     test_loss = 0
     correct = None
+    correct_k = None
     n = 0
     with torch.no_grad():
         for batch_idx, (data, target) in enumerate(test_loader):
             output = model(data)
             test_loss += criterion(output, target)
             correct = count_correct(output, target, correct)
+            if topk is not None:
+                correct_k = count_correct(output, target, correct_k, topk=topk)
             n += 1
     test_loss /= max(1, n)
     correct = int(correct.sum().item()) if correct is not None else 0
@@ -129,6 +134,11 @@ def test_model(model, test_loader, criterion, print_fn=print):
             float(test_loss), correct, total, 100.0 * correct / total
         )
     )
+    if topk is not None:
+        import sys
+
+        ck = int(correct_k.sum().item()) if correct_k is not None else 0
+        print("[cdp] top-{} accuracy: {}/{} ({:.0f}%)".format(topk, ck, total, 100.0 * ck / total), file=sys.stderr)
     return float(test_loss), correct
 
 
@@ -162,7 +172,9 @@ def run(rank, size, epochs, batch_size, args):
         kind = "rccl-native" if dist.native_communicator() is not None else "torch-" + str(dist.get_backend())
         print(f"[cdp] rank {rank}: collectives on {kind}"
               + (f" ({dist.comm_fallback_reason()})" if dist.comm_fallback_reason() else ""), file=sys.stderr)
-    criterion = CrossEntropyLoss()
+    # label smoothing shapes the training loss only: the eval loss stays the plain cross-entropy
+    criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
+    eval_criterion = CrossEntropyLoss()
     model = get_model(args.model).to(device)
     sync = None
     strategy = args.strategy
@@ -199,7 +211,7 @@ def run(rank, size, epochs, batch_size, args):
         if device.type == "cuda":
             torch.cuda.synchronize()
         print("Training time after {} epoch is {}".format(epoch + 1, (time.time() - start_time)))
-        test_model(model, test_loader, criterion)
+        test_model(model, test_loader, eval_criterion, topk=args.eval_topk)
         if args.checkpoint_dir:
             save_checkpoint(os.path.join(args.checkpoint_dir, f"ckpt_{epoch + 1}.pt"), model, optimizer,
                             epoch=epoch + 1, rank=rank)
@@ -283,6 +295,10 @@ def parse_args(argv=None):
                    help="clip the global gradient 2-norm to this value inside the fused optimizer step")
     p.add_argument("--skip-nonfinite", action="store_true",
                    help="skip an optimizer step whose gradients hold an inf or a NaN")
+    p.add_argument("--label-smoothing", type=float, default=0.0, metavar="FLOAT",
+                   help="train against (1 - FLOAT) * onehot + FLOAT / classes (the test loss stays unsmoothed)")
+    p.add_argument("--eval-topk", type=int, default=None, metavar="K",
+                   help="also report the top-K accuracy of the test set (stderr; ties go to the lower class index)")
     p.add_argument("--bucket-cap-mb", type=float, default=None)
     p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
     p.add_argument("--seed", type=int, default=0)

@@ -269,10 +269,13 @@ void bn_bwd_apply_launch(const float* y, const float* gout, const float* stats, 
                          const unsigned char* rmask = nullptr);
 
 // misc.hip
+// eps: label smoothing in [0, 1] (target distribution (1 - eps) onehot + eps / C; 0: the plain kernels'
+// arithmetic); topk >= 1: a row counts as correct when fewer than topk logits rank above its target's
+// (ties to the lower index; 1: the argmax path)
 void xent_fwd_launch(const float* logits, const long long* tgt, int B, int C, float* loss, long long* correct,
-                     float* sum_out, hipStream_t st);
+                     float* sum_out, hipStream_t st, float eps = 0.f, int topk = 1);
 void xent_bwd_launch(const float* logits, const long long* tgt, const float* gscale, int B, int C, float* dlogits,
-                     hipStream_t st);
+                     hipStream_t st, float eps = 0.f);
 // counter (optional): a step counter the kernel advances by one (DeviceLoader.advance_with)
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
@@ -348,7 +351,7 @@ struct XentBnLink {
 };
 void xent_linear_bwd_launch(const float* logits, const long long* tgt, const float* gscale, const float* x,
                             const float* w, int B, int I, int O, float* dlogits, float* dx, float* dw, float* db,
-                            const XentBnLink& lk, hipStream_t st);
+                            const XentBnLink& lk, hipStream_t st, float eps = 0.f);
 void avgpool_fwd_launch(const float* x, int N, int HW, int C, float* y, hipStream_t st);
 void avgpool_bwd_launch(const float* gy, int N, int HW, int C, float* gx, hipStream_t st);
 // NHWC, C % 4 == 0; arg = window-local argmax tap (uint8, k*k <= 255)

@@ -25,9 +25,31 @@ namespace {
 // One block of 1024 threads. Narrow rows (C <= 64, e.g. CIFAR's 10 classes): one row per thread;
 // wide rows (ImageNet's 1000): one row per wave. Per-row loss = logsumexp - logit[target]; the mean
 // (fp64 block reduction, deterministic) and the top-1 correct count are written once.
+//
+// LS (label smoothing eps > 0, target distribution (1 - eps) onehot(t) + eps / C):
+//   loss = logsumexp(z) - (1 - eps) z_t - (eps / C) sum_c z_c
+//        = log(sum_c exp(z_c - mx)) + (1 - eps) (mx - z_t) - (eps / C) sum_c (z_c - mx)
+// TK (topk > 1): a row is correct when rank < topk, rank = #{c : z_c > z_t, or z_c == z_t and c < t}
+// (ties to the lower index, the argmax path's first-occurrence rule); not correct with a target out
+// of range or a NaN target logit. Without LS / TK the instantiation is the plain kernel: eps and
+// topk are not read.
+__device__ __forceinline__ float xent_ls_row(float lse_rel, float mx, float zt, float sz, float eps, int C) {
+  return lse_rel + (1.f - eps) * (mx - zt) - (eps / (float)C) * sz;
+}
+__device__ __forceinline__ int xent_above(float v, int c, float zt, int t) {
+  return (v > zt || (v == zt && c < t)) ? 1 : 0;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
+template <bool LS, bool TK>
 __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ tgt,
                                                        int B, int C, float* __restrict__ loss,
-                                                       long long* __restrict__ correct, float* __restrict__ sum_out) {
+                                                       long long* __restrict__ correct, float* __restrict__ sum_out,
+                                                       float eps, int topk) {
   __shared__ double red[16];
   __shared__ int redc[16];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -46,8 +68,23 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
       for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
       const long long t = tgt[r];
       const bool tok = t >= 0 && t < C;  // out-of-range targets poison the loss instead of reading OOB
-      acc += tok ? (double)(logf(se) + mx - row[t]) : (double)NAN;
-      nc += (tok && am == (int)t) ? 1 : 0;
+      if (LS) {
+        float sz = 0.f;
+        for (int c = 0; c < C; ++c) sz += row[c] - mx;
+        acc += tok ? (double)xent_ls_row(logf(se), mx, row[t], sz, eps, C) : (double)NAN;
+      } else {
+        acc += tok ? (double)(logf(se) + mx - row[t]) : (double)NAN;
+      }
+      if (TK) {
+        if (tok) {
+          const float zt = row[t];
+          int rank = 0;
+          for (int c = 0; c < C; ++c) rank += xent_above(row[c], c, zt, (int)t);
+          nc += (zt == zt && rank < topk) ? 1 : 0;
+        }
+      } else {
+        nc += (tok && am == (int)t) ? 1 : 0;
+      }
     }
   } else if (C <= 1024) {
     // a wave's rows r = wid + 16 k (the loop below's assignment and order) four at a time, every
@@ -86,11 +123,38 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
         for (int j = 0; j < J; ++j)
           if (lane + 64 * j < C) se += expf(v[k][j] - mx);
         se = wave_sum(se);
+        float sz = 0.f;
+        if (LS) {
+#pragma unroll
+          for (int j = 0; j < J; ++j)
+            if (lane + 64 * j < C) sz += v[k][j] - mx;
+          sz = wave_sum(sz);
+        }
+        int rank = 0;
+        bool tkok = false;
+        if (TK) {
+          // every lane reads the row's target and target logit (one address: a broadcast load)
+          const long long t = tgt[r];
+          if (t >= 0 && t < C) {
+            const float zt = logits[(long long)r * C + t];
+            tkok = zt == zt;
+#pragma unroll
+            for (int j = 0; j < J; ++j)
+              if (lane + 64 * j < C) rank += xent_above(v[k][j], lane + 64 * j, zt, (int)t);
+          }
+          rank = wave_sum_i(rank);
+        }
         if (lane == 0) {
           const long long t = tgt[r];
           const bool tok = t >= 0 && t < C;
-          acc += tok ? (double)(logf(se) + mx - logits[(long long)r * C + t]) : (double)NAN;
-          nc += (tok && am == (int)t) ? 1 : 0;
+          if (LS)
+            acc += tok ? (double)xent_ls_row(logf(se), mx, logits[(long long)r * C + t], sz, eps, C) : (double)NAN;
+          else
+            acc += tok ? (double)(logf(se) + mx - logits[(long long)r * C + t]) : (double)NAN;
+          if (TK)
+            nc += (tkok && rank < topk) ? 1 : 0;
+          else
+            nc += (tok && am == (int)t) ? 1 : 0;
         }
       }
     }
@@ -113,11 +177,33 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
       float se = 0.f;
       for (int c = lane; c < C; c += 64) se += expf(row[c] - mx);
       se = wave_sum(se);
+      float sz = 0.f;
+      if (LS) {
+        for (int c = lane; c < C; c += 64) sz += row[c] - mx;
+        sz = wave_sum(sz);
+      }
+      int rank = 0;
+      bool tkok = false;
+      if (TK) {
+        const long long t = tgt[r];
+        if (t >= 0 && t < C) {
+          const float zt = row[t];
+          tkok = zt == zt;
+          for (int c = lane; c < C; c += 64) rank += xent_above(row[c], c, zt, (int)t);
+        }
+        rank = wave_sum_i(rank);
+      }
       if (lane == 0) {
         const long long t = tgt[r];
         const bool tok = t >= 0 && t < C;
-        acc += tok ? (double)(logf(se) + mx - row[t]) : (double)NAN;
-        nc += (tok && am == (int)t) ? 1 : 0;
+        if (LS)
+          acc += tok ? (double)xent_ls_row(logf(se), mx, row[t], sz, eps, C) : (double)NAN;
+        else
+          acc += tok ? (double)(logf(se) + mx - row[t]) : (double)NAN;
+        if (TK)
+          nc += (tkok && rank < topk) ? 1 : 0;
+        else
+          nc += (tok && am == (int)t) ? 1 : 0;
       }
     }
   }
@@ -142,10 +228,11 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
   }
 }
 
-// dlogits = (softmax - onehot) * gscale[0] / B
+// dlogits = (softmax - onehot) * gscale[0] / B; LS: (softmax - (1 - eps) onehot - eps / C) * gscale[0] / B
+template <bool LS>
 __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ tgt,
                                                       const float* __restrict__ gscale, int B, int C,
-                                                      float* __restrict__ dlogits) {
+                                                      float* __restrict__ dlogits, float eps) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= B) return;
@@ -159,9 +246,13 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
   const float k = gscale[0] / (float)B;
   const float inv = 1.f / se;
   const long long t = tgt[r];
+  const float on = 1.f - eps, off = eps / (float)C;  // (LS only)
   for (int c = lane; c < C; c += 64) {
     const float sm = expf(row[c] - mx) * inv;
-    dlogits[(long long)r * C + c] = (sm - (c == t ? 1.f : 0.f)) * k;
+    if (LS)
+      dlogits[(long long)r * C + c] = (sm - (c == t ? on : 0.f) - off) * k;
+    else
+      dlogits[(long long)r * C + c] = (sm - (c == t ? 1.f : 0.f)) * k;
   }
 }
 
@@ -815,15 +906,20 @@ __global__ __launch_bounds__(256) void small_linear_bwd_kernel(const float* __re
 //                            statistics launch of its own (ops/functional.py _BNLink)
 //   blocks [nbx, nbx + nbw)  dW, last block db (small_linear_bwd_body)
 // Three launches (xent_bwd, small_linear_bwd, bn_bwd_reduce) and two kernel boundaries less per step.
+// LS (label smoothing eps > 0): dlogits = (softmax - (1 - eps) onehot(t) - eps / O) * gscale / B, as
+// xent_bwd_kernel<true>; the sdy tile then carries the smoothed gradient and nothing else differs.
+template <bool LS>
 __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __restrict__ logits,
                                                               const long long* __restrict__ tgt,
                                                               const float* __restrict__ gscale,
                                                               const float* __restrict__ x, const float* __restrict__ w,
                                                               int B, int I, int O, float* __restrict__ dlogits,
                                                               float* __restrict__ dx, float* __restrict__ dw,
-                                                              float* __restrict__ db, int nbx, int nbw, XentBnLink lk) {
+                                                              float* __restrict__ db, int nbx, int nbw, XentBnLink lk,
+                                                              float eps) {
   __shared__ float sdy[kXentLinMax];
   const float k = gscale[0] / (float)B;
+  const float on = 1.f - eps, off = eps / (float)O;  // (LS only)
   for (int r = threadIdx.x; r < B; r += 256) {
     const float* row = logits + (long long)r * O;
     float v[SL_MAXO];
@@ -834,15 +930,32 @@ __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __res
       mx = fmaxf(mx, v[o]);
     }
     float se = 0.f;
+    if (LS) {
+      // the sum in the order of xent_bwd_kernel's wave_sum (a xor butterfly over the lanes o < 16;
+      // o >= O adds exact zeros): the smoothed gradient of the fused and of the unfused classifier
+      // backward are then the same bits. (The plain sum below differs from that kernel's by an ulp.)
+      static_assert(SL_MAXO == 16, "the butterfly below is written for 16 classes");
+      float e[SL_MAXO];
 #pragma unroll
-    for (int o = 0; o < SL_MAXO; ++o)
-      if (o < O) se += expf(v[o] - mx);
+      for (int o = 0; o < SL_MAXO; ++o) e[o] = o < O ? expf(v[o] - mx) : 0.f;
+#pragma unroll
+      for (int h = SL_MAXO / 2; h > 0; h >>= 1) {
+#pragma unroll
+        for (int o = 0; o < h; ++o) e[o] += e[o + h];
+      }
+      se = e[0];
+    } else {
+#pragma unroll
+      for (int o = 0; o < SL_MAXO; ++o)
+        if (o < O) se += expf(v[o] - mx);
+    }
     const float inv = 1.f / se;
     const long long t = tgt[r];
 #pragma unroll
     for (int o = 0; o < SL_MAXO; ++o) {
       if (o >= O) break;
-      const float d = (expf(v[o] - mx) * inv - (o == t ? 1.f : 0.f)) * k;
+      const float d = LS ? (expf(v[o] - mx) * inv - (o == t ? on : 0.f) - off) * k
+                         : (expf(v[o] - mx) * inv - (o == t ? 1.f : 0.f)) * k;
       sdy[r * O + o] = d;
       if (blockIdx.x == 0) dlogits[(long long)r * O + o] = d;
     }
@@ -1051,12 +1164,19 @@ __global__ __launch_bounds__(256) void wtrans_sub_kernel(const float* __restrict
 }  // namespace
 
 void xent_fwd_launch(const float* logits, const long long* tgt, int B, int C, float* loss, long long* correct,
-                     float* sum_out, hipStream_t st) {
-  hipLaunchKernelGGL(xent_fwd_kernel, dim3(1), dim3(1024), 0, st, logits, tgt, B, C, loss, correct, sum_out);
+                     float* sum_out, hipStream_t st, float eps, int topk) {
+  if (!(eps >= 0.f && eps <= 1.f) || topk < 1) throw std::runtime_error("xent_fwd: label smoothing in [0, 1], topk >= 1");
+  // eps == 0 and topk == 1 take the plain instantiation: the arithmetic of a call without them
+  const bool ls = eps != 0.f, tk = topk > 1;
+  auto kern = ls ? (tk ? xent_fwd_kernel<true, true> : xent_fwd_kernel<true, false>)
+                 : (tk ? xent_fwd_kernel<false, true> : xent_fwd_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, st, logits, tgt, B, C, loss, correct, sum_out, eps, topk);
 }
 void xent_bwd_launch(const float* logits, const long long* tgt, const float* gscale, int B, int C, float* dlogits,
-                     hipStream_t st) {
-  hipLaunchKernelGGL(xent_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, st, logits, tgt, gscale, B, C, dlogits);
+                     hipStream_t st, float eps) {
+  if (!(eps >= 0.f && eps <= 1.f)) throw std::runtime_error("xent_bwd: label smoothing in [0, 1]");
+  auto kern = eps != 0.f ? xent_bwd_kernel<true> : xent_bwd_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, st, logits, tgt, gscale, B, C, dlogits, eps);
 }
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
@@ -1224,13 +1344,15 @@ void small_linear_bwd_launch(const float* dy, const float* x, const float* w, in
 }
 void xent_linear_bwd_launch(const float* logits, const long long* tgt, const float* gscale, const float* x,
                             const float* w, int B, int I, int O, float* dlogits, float* dx, float* dw, float* db,
-                            const XentBnLink& lk, hipStream_t st) {
+                            const XentBnLink& lk, hipStream_t st, float eps) {
   if (O > SL_MAXO || (long long)B * O > kXentLinMax) throw std::runtime_error("xent_linear_bwd: classifier too wide");
   if (lk.y && (!dx || lk.ps < 2 || lk.ps > 3)) throw std::runtime_error("xent_linear_bwd: BN link needs dX");
+  if (!(eps >= 0.f && eps <= 1.f)) throw std::runtime_error("xent_linear_bwd: label smoothing in [0, 1]");
   const int nbx = dx ? ((I + 15) / 16) * xent_lin_chunks(B) : 0;
   const int nbw = (I + 15) / 16;
-  hipLaunchKernelGGL(xent_linear_bwd_kernel, dim3(nbx + nbw + 1), dim3(256), 0, st, logits, tgt, gscale, x, w, B, I, O,
-                     dlogits, dx, dw, db, nbx, nbw, lk);
+  auto kern = eps != 0.f ? xent_linear_bwd_kernel<true> : xent_linear_bwd_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(nbx + nbw + 1), dim3(256), 0, st, logits, tgt, gscale, x, w, B, I, O, dlogits, dx, dw,
+                     db, nbx, nbw, lk, eps);
 }
 void avgpool_fwd_launch(const float* x, int N, int HW, int C, float* y, hipStream_t st) {
   if ((long long)N * HW * C >= (1LL << 31)) throw std::runtime_error("avgpool: tensor too large");

@@ -83,14 +83,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_bwd", &linear_bwd, py::arg("gy"), py::arg("x"), py::arg("w"), py::arg("need_dx"),
         py::arg("has_bias"), py::arg("dw_out") = py::none(), py::arg("db_out") = py::none());
-  m.def("xent_fwd", &xent_fwd, py::arg("logits"), py::arg("target"), py::arg("correct") = py::none());
-  m.def("xent_bwd", &xent_bwd);
+  m.def("xent_fwd", &xent_fwd, py::arg("logits"), py::arg("target"), py::arg("correct") = py::none(),
+        py::arg("label_smoothing") = 0.0, py::arg("topk") = 1);
+  m.def("xent_bwd", &xent_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("label_smoothing") = 0.0);
   m.def("gemm_log", &gemm_log, py::arg("clear") = false,
         "CDP_GEMM_LOG=1: (kind, M, N, K, bm, bn, splits) of every conv / weight-gradient GEMM launch so far");
   m.def("xent_linear_bwd", &xent_linear_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("x"),
         py::arg("w"), py::arg("need_dx"), py::arg("has_bias"), py::arg("dw_out") = py::none(),
         py::arg("db_out") = py::none(), py::arg("link_y") = py::none(), py::arg("link_stats") = py::none(),
         py::arg("link_pool") = false, py::arg("link_relu") = false, py::arg("link_ps") = 2,
+        py::arg("label_smoothing") = 0.0,
         "CrossEntropy backward + narrow Linear backward in one launch (+ the BN backward partials of the block "
         "that produced the Linear's input, link_*): {dlogits, dx, dw, db, part}");
   py::class_<LarsStep>(m, "LarsStep", "the LARS block of sgd_step / sgd_step_prep (default: off)")

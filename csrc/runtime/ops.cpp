@@ -1810,9 +1810,15 @@ std::vector<at::Tensor> linear_bwd(const at::Tensor& gy_, const at::Tensor& x_, 
 
 // ---------------------------------------------------------------- cross entropy
 // {loss (0-dim), correct (int64 [1], accumulated in place when given)}
-at::Tensor xent_fwd(const at::Tensor& logits_, const at::Tensor& target, const c10::optional<at::Tensor>& correct) {
+// label_smoothing eps: loss against (1 - eps) onehot + eps / C; topk: a row is correct when fewer than
+// topk logits rank above its target's (ties to the lower index)
+at::Tensor xent_fwd(const at::Tensor& logits_, const at::Tensor& target, const c10::optional<at::Tensor>& correct,
+                    double label_smoothing, int64_t topk) {
   check_f32_cuda(logits_, "logits");
   TORCH_CHECK(target.scalar_type() == at::kLong, "target must be int64");
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent_fwd: label_smoothing must be in [0, 1], got ",
+              label_smoothing);
+  TORCH_CHECK(topk >= 1, "xent_fwd: topk must be >= 1, got ", topk);
   const at::Tensor logits = logits_.contiguous();
   const at::Tensor tgt = target.contiguous();
   const int B = logits.size(0), C = logits.size(1);
@@ -1820,17 +1826,20 @@ at::Tensor xent_fwd(const at::Tensor& logits_, const at::Tensor& target, const c
   long long* cp = nullptr;
   if (correct.has_value() && correct->defined()) cp = reinterpret_cast<long long*>(correct->data_ptr<int64_t>());
   xent_fwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(tgt.data_ptr<int64_t>()), B, C, loss.data_ptr<float>(), cp, nullptr,
-                  cur_stream());
+                  cur_stream(), (float)label_smoothing, (int)std::min<int64_t>(topk, 0x7fffffff));
   return loss;
 }
 
-at::Tensor xent_bwd(const at::Tensor& gloss, const at::Tensor& logits_, const at::Tensor& target) {
+at::Tensor xent_bwd(const at::Tensor& gloss, const at::Tensor& logits_, const at::Tensor& target,
+                    double label_smoothing) {
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent_bwd: label_smoothing must be in [0, 1], got ",
+              label_smoothing);
   const at::Tensor logits = logits_.contiguous();
   const at::Tensor g = gloss.to(at::kFloat).contiguous();
   const int B = logits.size(0), C = logits.size(1);
   at::Tensor d = at::empty_like(logits);
   xent_bwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(target.contiguous().data_ptr<int64_t>()), g.data_ptr<float>(), B, C,
-                  d.data_ptr<float>(), cur_stream());
+                  d.data_ptr<float>(), cur_stream(), (float)label_smoothing);
   return d;
 }
 
@@ -1842,7 +1851,9 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
                                         const c10::optional<at::Tensor>& dw_out, const c10::optional<at::Tensor>& db_out,
                                         const c10::optional<at::Tensor>& link_y,
                                         const c10::optional<at::Tensor>& link_stats, bool link_pool, bool link_relu,
-                                        int64_t link_ps) {
+                                        int64_t link_ps, double label_smoothing) {
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0,
+              "xent_linear_bwd: label_smoothing must be in [0, 1], got ", label_smoothing);
   const at::Tensor logits = logits_.contiguous(), x = x_.contiguous(), w = w_.contiguous();
   const at::Tensor g = gloss.to(at::kFloat).contiguous();
   const at::Tensor tgt = target.contiguous();
@@ -1878,7 +1889,7 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
   xent_linear_bwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(tgt.data_ptr<int64_t>()),
                          g.data_ptr<float>(), x.data_ptr<float>(), w.data_ptr<float>(), B, I, O, dl.data_ptr<float>(),
                          need_dx ? dx.data_ptr<float>() : nullptr, dw.data_ptr<float>(),
-                         has_bias ? db.data_ptr<float>() : nullptr, lk, cur_stream());
+                         has_bias ? db.data_ptr<float>() : nullptr, lk, cur_stream(), (float)label_smoothing);
   return {dl, dx, dw, db, part};
 }
 

@@ -71,14 +71,17 @@ at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
 std::vector<at::Tensor> linear_bwd(const at::Tensor& gy, const at::Tensor& x, const at::Tensor& w, bool need_dx,
                                    bool has_bias, const c10::optional<at::Tensor>& dw_out,
                                    const c10::optional<at::Tensor>& db_out);
-at::Tensor xent_fwd(const at::Tensor& logits, const at::Tensor& target, const c10::optional<at::Tensor>& correct);
-at::Tensor xent_bwd(const at::Tensor& gloss, const at::Tensor& logits, const at::Tensor& target);
+at::Tensor xent_fwd(const at::Tensor& logits, const at::Tensor& target, const c10::optional<at::Tensor>& correct,
+                    double label_smoothing = 0.0, int64_t topk = 1);
+at::Tensor xent_bwd(const at::Tensor& gloss, const at::Tensor& logits, const at::Tensor& target,
+                    double label_smoothing = 0.0);
 std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tensor& logits, const at::Tensor& target,
                                         const at::Tensor& x, const at::Tensor& w, bool need_dx, bool has_bias,
                                         const c10::optional<at::Tensor>& dw_out, const c10::optional<at::Tensor>& db_out,
                                         const c10::optional<at::Tensor>& link_y = c10::nullopt,
                                         const c10::optional<at::Tensor>& link_stats = c10::nullopt,
-                                        bool link_pool = false, bool link_relu = false, int64_t link_ps = 2);
+                                        bool link_pool = false, bool link_relu = false, int64_t link_ps = 2,
+                                        double label_smoothing = 0.0);
 // The LARS block of a fused SGD step (csrc/kernels/lars.h): descriptor, meta and partials from
 // lars_plan, the partials filled by lars_norms just before; ratios: one float per parameter.
 // Without a descriptor the step is plain SGD.

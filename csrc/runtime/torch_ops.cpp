@@ -37,8 +37,8 @@ at::Tensor linear_cuda(const at::Tensor& x, const at::Tensor& w, const c10::opti
   return linear_fwd(x, w, b);
 }
 
-at::Tensor cross_entropy_cuda(const at::Tensor& logits, const at::Tensor& target) {
-  return xent_fwd(logits, target, c10::nullopt);
+at::Tensor cross_entropy_cuda(const at::Tensor& logits, const at::Tensor& target, double label_smoothing) {
+  return xent_fwd(logits, target, c10::nullopt, label_smoothing, 1);
 }
 
 std::tuple<at::Tensor, at::Tensor> max_pool2d_cuda(const at::Tensor& x, int64_t k, int64_t s, int64_t p) {
@@ -109,7 +109,7 @@ TORCH_LIBRARY(cdp, m) {
   m.def("conv2d_dgrad(Tensor dy, Tensor w, int[] in_shape, int stride, int pad) -> Tensor");
   m.def("conv2d_wgrad(Tensor dy, Tensor x, int[] w_shape, int stride, int pad) -> Tensor");
   m.def("linear(Tensor x, Tensor w, Tensor? bias) -> Tensor");
-  m.def("cross_entropy(Tensor logits, Tensor target) -> Tensor");
+  m.def("cross_entropy(Tensor logits, Tensor target, float label_smoothing=0.0) -> Tensor");
   m.def("max_pool2d(Tensor x, int k, int s, int p) -> (Tensor, Tensor)");
 }
 
