@@ -25,6 +25,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _gemm_util import check_bound, make_data
+
 pytestmark = pytest.mark.gpu
 
 ENGINES = ["f16x2", "x3", "f32"]
@@ -55,28 +57,11 @@ def cl(t):
 
 
 def _data(kind, shape, gen):
-    t = torch.randn(shape, generator=gen, dtype=torch.float64)
-    if kind == "heavy":
-        t = t * torch.exp(2.0 * torch.randn(shape, generator=gen, dtype=torch.float64))
-    elif kind == "image_spread":  # image n scaled by 2^(-42 n / (N-1)): the last one by 2^-42
-        n = shape[0]
-        t = t * torch.pow(2.0, -42.0 * torch.arange(n, dtype=torch.float64) / max(1, n - 1)).view(-1, 1, 1, 1)
-    elif kind == "channel_spread":  # channel c scaled by 2^(-(3c mod 43))
-        t = t * torch.pow(2.0, -((3.0 * torch.arange(shape[1], dtype=torch.float64)) % 43)).view(1, -1, 1, 1)
-    elif kind == "pixel_spread":  # inside every image, all pixels but the first 2^-40 below it
-        s = torch.full(shape[2:], 2.0 ** -40, dtype=torch.float64)
-        s[0, 0] = 1.0
-        t = t * s.view(1, 1, *shape[2:])
-    return t.float()
+    return make_data(kind, shape, gen)
 
 
 def _check(name, got, ref, absref, K):
-    c = 4.0
-    bound = c * (2.0 ** -22 + K * 2.0 ** -24) * absref + 1e-300
-    err = (got.double().cpu() - ref).abs()
-    ratio = (err / bound).max().item()
-    assert ratio <= 1.0, f"{name}: worst |err|/bound = {ratio:.3g} (K={K})"
-    return ratio
+    return check_bound(name, got, ref, absref, K)
 
 
 KINDS = ["normal", "heavy", "image_spread", "channel_spread"]

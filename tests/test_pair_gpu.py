@@ -9,7 +9,11 @@ one grid) against the two separate launches (CDP_BWD_PAIR=0, read on every call)
 * An NCHW-contiguous input that needs a gradient: the weight-gradient GEMM held back for the pair
   reads a channels_last copy of x and |max| partials made inside the backward call; both must stay
   alive until the paired launch is enqueued (else dX, allocated in between, may reuse their memory).
+* Every paired instantiation -- the planner reaches only the pairs that beat its cost model -- forced
+  through set_gemm_override on a small block whose two GEMMs have M and N tails under every tile.
 """
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -146,3 +150,70 @@ def test_tuned_plans_are_the_planners_choice():
         assert list(lib.plan_info("dgrad", 512, 512, 4608)) == list(lib.plan_info("conv", 512, 512, 4608))
     finally:
         lib.set_conv_gemm(orig)
+
+
+# ------------------------------------------------------------- every paired instantiation
+# The 16 pairs of 256-thread tiles ({64, 128} x {64, 128} data-gradient tiles beside the same four
+# weight-gradient tiles, bwd_pair_d*.hip) and the 512-thread 256x128 pair (bwd_pair.hip), forced
+# through set_gemm_override on a block whose GEMMs have M and N tails under every tile: 96 -> 160
+# channels, 3 images of 10x10 (data gradient M 300, N 96, K 1440; weight gradient 160 x 864 over 300
+# rows = ten 32-row steps, the last one 12 rows). The conv override also moves the block's forward
+# GEMM to the same tile, which changes nothing that is compared here.
+TAIL_BLOCK = (3, 96, 160, 10)  # N, Ci, Co, HW
+TILES4 = [(64, 64), (64, 128), (128, 64), (128, 128)]
+PAIRS = [(d, w) for d in TILES4 for w in TILES4] + [((256, 128), (256, 128))]
+
+
+@functools.lru_cache(maxsize=None)
+def _tail_block():
+    N, Ci, Co, HW = TAIL_BLOCK
+    conv, bn = _block(Ci, Co, 31)
+    x = torch.relu(torch.randn(N, Ci, HW, HW, device="cuda")).contiguous(memory_format=torch.channels_last)
+    gy = torch.randn(N, Co, HW, HW, device="cuda").contiguous(memory_format=torch.channels_last)
+    dx_r, dw_r = _fp64(x, conv, bn, False, gy, relu=False)
+    return conv, bn, x, gy, dx_r.cuda(), dw_r.cuda()
+
+
+def _forced_tail_grads(monkeypatch, dtile, wtile, splits):
+    """(dX, dW, paired launches) of the tail block with and without the pair under forced plans."""
+    N, Ci, Co, HW = TAIL_BLOCK
+    conv, bn, x, gy, _, _ = _tail_block()
+    lib = _lib()
+    orig = lib.get_conv_gemm()
+    try:
+        lib.set_conv_gemm("f16x2")
+        lib.set_gemm_override("conv", *dtile, splits)
+        lib.set_gemm_override("wgrad", *wtile, splits)
+        assert list(lib.plan_info("dgrad", N * HW * HW, Ci, 9 * Co)) == [*dtile, splits]
+        assert list(lib.plan_info("wgrad", N * HW * HW, Co, 9 * Ci)) == [*wtile, splits]
+        paired = _grads(monkeypatch, True, x, conv, bn, False, gy, relu=False)
+        separate = _grads(monkeypatch, False, x, conv, bn, False, gy, relu=False)
+    finally:
+        lib.set_conv_gemm(orig)
+        lib.set_gemm_override("conv", 0, 0, 0)
+        lib.set_gemm_override("wgrad", 0, 0, 0)
+    return paired, separate
+
+
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("dtile,wtile", [pytest.param(d, w, id=f"d{d[0]}x{d[1]}-w{w[0]}x{w[1]}") for d, w in PAIRS])
+def test_every_paired_instantiation_at_tail_shape(monkeypatch, dtile, wtile, splits):
+    (dx_p, dw_p, n_pair), (dx_s, dw_s, n_sep) = _forced_tail_grads(monkeypatch, dtile, wtile, splits)
+    assert n_pair == 1 and n_sep == 0, (n_pair, n_sep)
+    # the tolerances of test_paired_gradients_match_separate_launches_and_fp64, for its reasons
+    assert _rel(dx_p, dx_s) <= 1e-6 and _rel(dw_p, dw_s) <= 1e-6, (_rel(dx_p, dx_s), _rel(dw_p, dw_s))
+    _, _, _, _, dx_r, dw_r = _tail_block()
+    e_dx, e_dw = _rel(dx_p, dx_r), _rel(dw_p, dw_r)
+    assert e_dx <= 1e-5 and e_dw <= 1e-5, (e_dx, e_dw)
+
+
+@pytest.mark.parametrize("dtile,wtile", [((256, 128), (128, 128)), ((128, 128), (256, 128))],
+                         ids=["d256x128-w128x128", "d128x128-w256x128"])
+def test_mixed_workgroup_sizes_are_not_paired(monkeypatch, dtile, wtile):
+    """A 512-thread tile beside a 256-thread one has no paired kernel (bwd_pair_ok): the two GEMMs
+    run as separate launches, and the gradients are still right."""
+    (dx_p, dw_p, n_pair), (dx_s, dw_s, n_sep) = _forced_tail_grads(monkeypatch, dtile, wtile, 3)
+    assert n_pair == 0 and n_sep == 0, (n_pair, n_sep)
+    assert _rel(dx_p, dx_s) <= 1e-6 and _rel(dw_p, dw_s) <= 1e-6
+    _, _, _, _, dx_r, dw_r = _tail_block()
+    assert _rel(dx_p, dx_r) <= 1e-5 and _rel(dw_p, dw_r) <= 1e-5, (_rel(dx_p, dx_r), _rel(dw_p, dw_r))
