@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Iterator, List, Optional
+from typing import Iterator, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -147,16 +147,46 @@ class DistributedSampler:
         return self.num_samples
 
 
+class MixTarget(NamedTuple):
+    """The target of a mixed batch (mixup / CutMix): ``CrossEntropyLoss`` takes it in place of the int64
+    target and computes ``lam * CE(z, target) + (1 - lam) * CE(z, target_b)``.
+
+    ``target_b[b]`` is the label of image ``B - 1 - b``, the image that ``b`` was mixed with; ``lam`` is a
+    1-element fp32 view of ``info[1]``; ``info`` is the batch's published row
+    ``{mode (0 none, 1 mixup, 2 cutmix), lam, lam_raw, y0, y1, x0, x1, 0}``."""
+
+    target: torch.Tensor
+    target_b: torch.Tensor
+    lam: torch.Tensor
+    info: torch.Tensor
+
+
+MIX_MODES = ("none", "mixup", "cutmix")
+
+
 class DeviceLoader:
     """Batches ``(data[B,C,H,W] fp32 channels_last, target[B] int64)`` from a device-resident dataset.
 
     ``train=True`` applies RandomCrop(pad)+RandomHorizontalFlip on the device; normalisation always.
     ``sampler`` (e.g. :class:`DistributedSampler`) picks the indices; without one the order is
     sequential (``shuffle=False``) or a seeded permutation (``shuffle=True``).
+
+    ``mixup_alpha`` / ``cutmix_alpha`` > 0 (and ``train=True``) mix every batch in the same kernel: one
+    ``lam ~ Beta(alpha, alpha)`` per batch, drawn on the device from the step counter; image ``b`` is
+    paired with image ``B - 1 - b``. A batch is mixed with probability ``mix_prob``; with both alphas set
+    it is CutMix with probability ``mix_switch_prob``, else mixup. The target is then a
+    :class:`MixTarget`. With both alphas 0 the loader returns exactly what it returns without them.
     """
 
     def __init__(self, dataset: ImageDataset, batch_size: int, sampler=None, shuffle: bool = False,
-                 train: bool = True, drop_last: bool = False, seed: int = 0):
+                 train: bool = True, drop_last: bool = False, seed: int = 0, mixup_alpha: float = 0.0,
+                 cutmix_alpha: float = 0.0, mix_prob: float = 1.0, mix_switch_prob: float = 0.5):
+        if not (mixup_alpha >= 0.0 and cutmix_alpha >= 0.0):
+            raise ValueError(f"mixup_alpha and cutmix_alpha must be >= 0. Got: {mixup_alpha}, {cutmix_alpha}")
+        if not (0.0 <= mix_prob <= 1.0 and 0.0 <= mix_switch_prob <= 1.0):
+            raise ValueError(f"mix_prob and mix_switch_prob must be in [0, 1]. Got: {mix_prob}, {mix_switch_prob}")
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.mix_prob, self.mix_switch_prob = float(mix_prob), float(mix_switch_prob)
         self.ds, self.batch_size, self.sampler, self.shuffle = dataset, batch_size, sampler, shuffle
         self.train, self.drop_last, self.seed = train, drop_last, seed
         self.dev = dataset.images.device
@@ -220,6 +250,11 @@ class DeviceLoader:
     def dataset(self):
         return self.ds
 
+    @property
+    def mixing(self) -> bool:
+        """Whether batches are mixed (an alpha > 0 on a training loader) and carry a :class:`MixTarget`."""
+        return self.train and (self.mixup_alpha > 0.0 or self.cutmix_alpha > 0.0)
+
     def batch(self, idx: torch.Tensor, offset: int, bsz: int, out: Optional[torch.Tensor] = None,
               nbatches: int = 0):
         """Produce one batch from ``idx[offset:offset+bsz]`` (graph-capturable on GPU).
@@ -236,18 +271,76 @@ class DeviceLoader:
         if self.dev.type == "cuda":
             C = _native.lib()
             target = torch.empty(bsz, dtype=torch.int64, device=self.dev)
-            data = C.augment(self.ds.images, idx, offset, bsz, self.ds.mean, self.ds.std, pad, flip, self._counter,
-                             self.seed, out, nbatches, self.ds.labels, target)
+            if self.mixing:
+                # the same launch draws the batch's mix from the step counter, applies it and publishes it
+                target_b = torch.empty(bsz, dtype=torch.int64, device=self.dev)
+                info = torch.empty(8, dtype=torch.float32, device=self.dev)
+                data = C.augment(self.ds.images, idx, offset, bsz, self.ds.mean, self.ds.std, pad, flip, self._counter,
+                                 self.seed, out, nbatches, self.ds.labels, target, mixup_alpha=self.mixup_alpha,
+                                 cutmix_alpha=self.cutmix_alpha, mix_prob=self.mix_prob,
+                                 mix_switch_prob=self.mix_switch_prob, mix=info, labels_b=target_b)
+                target = MixTarget(target, target_b, info[1:2], info)
+            else:
+                data = C.augment(self.ds.images, idx, offset, bsz, self.ds.mean, self.ds.std, pad, flip,
+                                 self._counter, self.seed, out, nbatches, self.ds.labels, target)
             if not self._external_advance:
                 C.counter_inc(self._counter)
             else:
                 self._check_one_batch_per_step()
             return data, target
+        ctr = int(self._counter.item()) if (nbatches > 0 or self.mixing) else None
         if nbatches > 0:
-            offset += (int(self._counter.item()) % nbatches) * bsz
-            if not pad:
-                self._counter += 1  # (the padded path advances it itself)
-        return self._cpu_batch(idx[offset : offset + bsz], pad, flip)
+            offset += (ctr % nbatches) * bsz
+        if ctr is not None and not pad:
+            self._counter += 1  # (the padded path advances it itself)
+        data, target = self._cpu_batch(idx[offset : offset + bsz], pad, flip)
+        if self.mixing:
+            return self._cpu_mix(data, target, ctr)
+        return data, target
+
+    def mix_schedule(self, first_counter: int, n: int) -> torch.Tensor:
+        """The rows ``{mode, lam, lam_raw, y0, y1, x0, x1, 0}`` that the batches at step counters
+        ``first_counter .. first_counter + n - 1`` publish (float32 ``[n, 8]``; GPU loaders)."""
+        H, W = self.ds.shape[:2]
+        return _native.lib().mix_params(self.seed, first_counter, n, self.mixup_alpha, self.cutmix_alpha,
+                                        self.mix_prob, self.mix_switch_prob, H, W)
+
+    def _cpu_mix(self, data, target, ctr):
+        """The device kernel's semantics on the host: one draw per batch from a generator of its own
+        (seeded apart from the crop / flip generator, whose draws are therefore unchanged), the pairing
+        ``b <-> B - 1 - b`` and the published box rule."""
+        H, W = data.shape[2], data.shape[3]
+        seed = (0x6D6978 << 40) + self.seed * 1000003 + ctr
+        g = torch.Generator().manual_seed(seed)
+        u_on, u_sw, u_y, u_x = torch.rand(4, generator=g, dtype=torch.float64).tolist()
+        mu, cm = self.mixup_alpha > 0.0, self.cutmix_alpha > 0.0
+        mode, lam, lam_raw, box = 0, 1.0, 1.0, (0, 0, 0, 0)
+        if u_on < self.mix_prob:
+            cut = cm and (not mu or u_sw < self.mix_switch_prob)
+            alpha = self.cutmix_alpha if cut else self.mixup_alpha
+            with torch.random.fork_rng(devices=[]):  # Beta samples from the default generator: seeded, then restored
+                torch.manual_seed(seed)
+                lam_raw = float(torch.distributions.Beta(torch.tensor(alpha), torch.tensor(alpha)).sample())
+            if cut:
+                r = math.sqrt(1.0 - lam_raw)
+                cut_h, cut_w = int(H * r), int(W * r)
+                cy, cx = min(int(u_y * H), H - 1), min(int(u_x * W), W - 1)
+                y0, y1 = max(cy - cut_h // 2, 0), min(cy + cut_h // 2, H)
+                x0, x1 = max(cx - cut_w // 2, 0), min(cx + cut_w // 2, W)
+                mode, box = 2, (y0, y1, x0, x1)
+                lam = 1.0 - (y1 - y0) * (x1 - x0) / (H * W)
+            else:
+                mode, lam = 1, lam_raw
+        info = torch.tensor([mode, lam, lam_raw, *box, 0], dtype=torch.float32)
+        lam = float(info[1])
+        partner = data.flip(0)
+        if mode == 1:
+            data = (data * lam + partner * (1.0 - lam)).contiguous(memory_format=torch.channels_last)
+        elif mode == 2:
+            data = data.clone(memory_format=torch.channels_last)
+            y0, y1, x0, x1 = box
+            data[:, :, y0:y1, x0:x1] = partner[:, :, y0:y1, x0:x1]
+        return data, MixTarget(target, target.flip(0), info[1:2], info)
 
     def _cpu_batch(self, sel, pad, flip):
         imgs = self.ds.images.index_select(0, sel).permute(0, 3, 1, 2).float().div_(255.0)  # NCHW

@@ -371,18 +371,20 @@ def linear(x, weight, bias=None):
 # --------------------------------------------------------------------------- cross entropy
 class _XEnt(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, label_smoothing=0.0):
-        ctx.save_for_backward(logits, target)
+    def forward(ctx, logits, target, label_smoothing=0.0, target_b=None, lam=None):
+        # target_b, lam (mixup / CutMix): the second target and its device-side weight ride along in all
+        # three native calls; lam is read by the kernels, so a replayed graph sees each step's value
+        ctx.save_for_backward(logits, target, target_b, lam)
         ctx.eps = float(label_smoothing)  # constant for a criterion: a host kernel argument of both passes
         # logits straight from a narrow native Linear (VGG's fc1): its backward rides on ours
         node = logits.grad_fn
         ctx.lin = node if (getattr(node, "narrow", False) and hasattr(node, "fused")
                            and logits.shape[0] * logits.shape[1] <= _XENT_LIN_MAX) else None
-        return _native.lib().xent_fwd(logits, target, None, ctx.eps)
+        return _native.lib().xent_fwd(logits, target, None, ctx.eps, 1, target_b, lam)
 
     @staticmethod
     def backward(ctx, g):
-        logits, target = ctx.saved_tensors
+        logits, target, target_b, lam = ctx.saved_tensors
         lin, ctx.lin = ctx.lin, None
         if lin is not None and os.environ.get("CDP_FUSED_CLASSIFIER", "1") != "0":
             x, w = lin.saved_tensors
@@ -395,25 +397,49 @@ class _XEnt(torch.autograd.Function):
             dl, dx, dw, db, part = _native.lib().xent_linear_bwd(
                 g.reshape(1), logits, target, x, w, nig[0], has_b, _slot(wp, nig[1]), _slot(bp, nig[2] and has_b),
                 li.y if link else None, li.stats if link else None, bool(li.pool) if link else False,
-                bool(li.relu) if link else False, li.ps if link else 2, label_smoothing=ctx.eps)
+                bool(li.relu) if link else False, li.ps if link else 2, label_smoothing=ctx.eps,
+                target_b=target_b, lam=lam)
             if link:  # the producer block's backward takes these partials if its gradient is this dX
                 li.part, li.gptr, li.gver = part, dx.data_ptr(), dx._version
             lin.fused = (dl, dx if nig[0] else None, dw, db if has_b else None)
-            return dl, None, None
-        return _native.lib().xent_bwd(g.reshape(1), logits, target, ctx.eps), None, None
+            return dl, None, None, None, None
+        return _native.lib().xent_bwd(g.reshape(1), logits, target, ctx.eps, target_b, lam), None, None, None, None
 
 
 _XENT_LIN_MAX = 8192  # batch x classes held in each block's LDS (csrc kernels.h kXentLinMax)
 
 
-def cross_entropy(logits, target, label_smoothing=0.0):
+def cross_entropy(logits, target, label_smoothing=0.0, target_b=None, lam=None):
     """Mean-reduced softmax cross-entropy (``torch.nn.CrossEntropyLoss()`` defaults), optionally against
-    the smoothed target distribution ``(1 - label_smoothing) * onehot + label_smoothing / C``."""
+    the smoothed target distribution ``(1 - label_smoothing) * onehot + label_smoothing / C``.
+
+    ``target_b`` and ``lam`` (together; mixup / CutMix): ``lam * CE(logits, target) + (1 - lam) *
+    CE(logits, target_b)`` with the same smoothing in both terms. ``lam`` is a float or a 1-element
+    tensor; on the GPU the kernels read it from the device, so it may change between graph replays."""
     if not 0.0 <= label_smoothing <= 1.0:
         raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
-    if use_native(logits) and logits.dim() == 2 and logits.dtype == torch.float32:
-        return _XEnt.apply(logits, target, float(label_smoothing))
-    return F.cross_entropy(logits, target, label_smoothing=label_smoothing)
+    if (target_b is None) != (lam is None):
+        raise ValueError("cross_entropy: target_b and lam must be given together")
+    native = use_native(logits) and logits.dim() == 2 and logits.dtype == torch.float32
+    if target_b is None:
+        if native:
+            return _XEnt.apply(logits, target, float(label_smoothing))
+        return F.cross_entropy(logits, target, label_smoothing=label_smoothing)
+    if torch.is_tensor(lam):
+        if lam.numel() != 1:
+            raise ValueError(f"cross_entropy: lam must hold one element (one lam per batch). Got: {tuple(lam.shape)}")
+    elif not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lam must be between 0.0 and 1.0. Got: {lam}")
+    if native:
+        if not torch.is_tensor(lam):
+            lam = torch.full((1,), float(lam), dtype=torch.float32, device=logits.device)
+        elif lam.dtype != torch.float32 or lam.device != logits.device:
+            lam = lam.to(device=logits.device, dtype=torch.float32)
+        return _XEnt.apply(logits, target, float(label_smoothing), target_b, lam.detach().reshape(1))
+    if torch.is_tensor(lam):
+        lam = lam.reshape(()).to(logits.device)
+    return (lam * F.cross_entropy(logits, target, label_smoothing=label_smoothing)
+            + (1 - lam) * F.cross_entropy(logits, target_b, label_smoothing=label_smoothing))
 
 
 def topk_hits(logits, target, topk):

@@ -10,6 +10,9 @@ class CrossEntropyLoss(nn.Module):
     ``label_smoothing`` in [0, 1] trains against ``(1 - label_smoothing) * onehot + label_smoothing / C``;
     0.0 (the default) is the reference's plain criterion.
 
+    ``target`` is an int64 tensor or the :class:`~..data.MixTarget` of a mixed batch (mixup / CutMix), for
+    which the loss is ``lam * CE(logits, target) + (1 - lam) * CE(logits, target_b)`` in the same kernels.
+
     Reference: ``torch.nn.CrossEntropyLoss().to(device)`` at ``/root/reference/src/Part 1/main.py:110``.
     """
 
@@ -20,6 +23,11 @@ class CrossEntropyLoss(nn.Module):
         self.label_smoothing = float(label_smoothing)
 
     def forward(self, logits, target):
+        from ..data import MixTarget
+
+        if isinstance(target, MixTarget):
+            return CF.cross_entropy(logits, target.target, self.label_smoothing, target_b=target.target_b,
+                                    lam=target.lam)
         return CF.cross_entropy(logits, target, self.label_smoothing)
 
     def extra_repr(self):

@@ -27,7 +27,7 @@ import time
 import torch
 
 from . import distributed as dist
-from .data import DeviceLoader, DistributedSampler, cifar10_binary, synthetic_cifar10, synthetic_imagenet
+from .data import MIX_MODES, DeviceLoader, DistributedSampler, MixTarget, cifar10_binary, synthetic_cifar10, synthetic_imagenet
 from .models import get_model
 from .ops import CrossEntropyLoss, count_correct
 from .optim import LARS, SGD
@@ -104,6 +104,13 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 tr = optimizer.trust_ratios
                 print("[cdp] rank {}: trust ratio in iter {} is min {} max {}".format(
                     rank, iter_number, float(tr.min()), float(tr.max())), file=sys.stderr)
+            if isinstance(target, MixTarget):
+                # mixup / CutMix: the window's last mix, as the loader's kernel published it (stderr, as above)
+                import sys
+
+                info = target.info.tolist()
+                print("[cdp] rank {}: mix in iter {} is mode {} lam {}".format(
+                    rank, iter_number, MIX_MODES[int(info[0])], info[1]), file=sys.stderr)
         if max_iters is not None and iter_number >= max_iters:
             break
         iter_number += 1
@@ -158,8 +165,10 @@ def run(rank, size, epochs, batch_size, args):
     device = dist.device() if dist.is_initialized() else args.device_obj
     training_set = build_data(args, device, True)
     train_sampler = DistributedSampler(training_set, num_replicas=size, rank=rank) if size > 1 else None
+    # mixup / CutMix shape the training batches only: the test loader below takes none of it
     train_loader = DeviceLoader(training_set, batch_size, sampler=train_sampler, shuffle=(size == 1), train=True,
-                                seed=args.seed)
+                                seed=args.seed, mixup_alpha=args.mixup_alpha, cutmix_alpha=args.cutmix_alpha,
+                                mix_prob=args.mix_prob, mix_switch_prob=args.mix_switch_prob)
     print("Size of training set is {}".format(len(train_loader)))
     test_set = build_data(args, device, False)
     test_loader = DeviceLoader(test_set, batch_size, shuffle=False, train=False)
@@ -297,6 +306,14 @@ def parse_args(argv=None):
                    help="skip an optimizer step whose gradients hold an inf or a NaN")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="FLOAT",
                    help="train against (1 - FLOAT) * onehot + FLOAT / classes (the test loss stays unsmoothed)")
+    p.add_argument("--mixup-alpha", type=float, default=0.0, metavar="FLOAT",
+                   help="mixup: blend every training batch with its reverse, lam ~ Beta(FLOAT, FLOAT) per batch (0: off)")
+    p.add_argument("--cutmix-alpha", type=float, default=0.0, metavar="FLOAT",
+                   help="CutMix: paste a box of the reversed batch, its area from Beta(FLOAT, FLOAT) (0: off)")
+    p.add_argument("--mix-prob", type=float, default=1.0, metavar="FLOAT",
+                   help="probability that a training batch is mixed at all (with --mixup-alpha / --cutmix-alpha)")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5, metavar="FLOAT",
+                   help="probability of CutMix over mixup when both alphas are set")
     p.add_argument("--eval-topk", type=int, default=None, metavar="K",
                    help="also report the top-K accuracy of the test set (stderr; ties go to the lower class index)")
     p.add_argument("--bucket-cap-mb", type=float, default=None)

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lars.h"
+#include "mix.h"
 
 namespace cdp {
 
@@ -272,10 +273,14 @@ void bn_bwd_apply_launch(const float* y, const float* gout, const float* stats, 
 // eps: label smoothing in [0, 1] (target distribution (1 - eps) onehot + eps / C; 0: the plain kernels'
 // arithmetic); topk >= 1: a row counts as correct when fewer than topk logits rank above its target's
 // (ties to the lower index; 1: the argmax path)
+// tgt_b, lam (both or neither; the MIX instantiations): a second target per row and its device-side weight,
+// loss = lam[0] CE_eps(z, tgt) + (1 - lam[0]) CE_eps(z, tgt_b); lam is read by the kernel like gscale, so a
+// replayed graph sees each step's value. Not together with correct.
 void xent_fwd_launch(const float* logits, const long long* tgt, int B, int C, float* loss, long long* correct,
-                     float* sum_out, hipStream_t st, float eps = 0.f, int topk = 1);
+                     float* sum_out, hipStream_t st, float eps = 0.f, int topk = 1, const long long* tgt_b = nullptr,
+                     const float* lam = nullptr);
 void xent_bwd_launch(const float* logits, const long long* tgt, const float* gscale, int B, int C, float* dlogits,
-                     hipStream_t st, float eps = 0.f);
+                     hipStream_t st, float eps = 0.f, const long long* tgt_b = nullptr, const float* lam = nullptr);
 // counter (optional): a step counter the kernel advances by one (DeviceLoader.advance_with)
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
@@ -304,11 +309,18 @@ void grad_sumsq_launch(const float* g, long long n, double* part, hipStream_t st
 // g *= coef in place (exact zeros stay zero under a NaN coef: the arena's pad floats); stats as ClipArgs
 void clip_scale_launch(float* g, long long n, const double* part, int nparts, float max_norm, float* stats,
                        hipStream_t st);
-// nbatches > 0: batch offset idx_off + (counter % nbatches) * B; labels_out[b] = labels[idx[...]] when given
+// nbatches > 0: batch offset idx_off + (counter % nbatches) * B; labels_out[b] = labels[idx[...]] when given.
+// cfg with an alpha > 0 (mix.h): mixup / CutMix of image b with image B - 1 - b in the same launch, the
+// batch's parameters published in mix[kMixRow], labels_b[b] = the partner's label
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,
                     unsigned long long seed, float* out, hipStream_t st, long long nbatches = 0,
-                    const long long* labels = nullptr, long long* labels_out = nullptr);
+                    const long long* labels = nullptr, long long* labels_out = nullptr,
+                    const MixCfg& cfg = MixCfg{0.f, 0.f, 1.f, 0.5f}, float* mix = nullptr,
+                    long long* labels_b = nullptr);
+// mix[i][kMixRow] = the row the augment kernel publishes at step counter first + i, i < n
+void mix_params_launch(unsigned long long seed, long long first, long long n, const MixCfg& cfg, int H, int W,
+                       float* mix, hipStream_t st);
 // zeros into the NHWC dX pixels of the sub-pixel parity classes set in mask (bit 2 ph + pw)
 // dst[0 .. bytes) = src[0 .. bytes) as a kernel (16-B accesses when both pointers and bytes allow)
 void copy_bytes_launch(void* dst, const void* src, long long bytes, hipStream_t st);
@@ -351,7 +363,8 @@ struct XentBnLink {
 };
 void xent_linear_bwd_launch(const float* logits, const long long* tgt, const float* gscale, const float* x,
                             const float* w, int B, int I, int O, float* dlogits, float* dx, float* dw, float* db,
-                            const XentBnLink& lk, hipStream_t st, float eps = 0.f);
+                            const XentBnLink& lk, hipStream_t st, float eps = 0.f, const long long* tgt_b = nullptr,
+                            const float* lam = nullptr);
 void avgpool_fwd_launch(const float* x, int N, int HW, int C, float* y, hipStream_t st);
 void avgpool_bwd_launch(const float* gy, int N, int HW, int C, float* gx, hipStream_t st);
 // NHWC, C % 4 == 0; arg = window-local argmax tap (uint8, k*k <= 255)

@@ -16,6 +16,7 @@
 #include "grad_clip.h"
 #include "lars.h"
 #include "kernels.h"
+#include "mix.h"
 #include "x3_common.h"
 
 namespace cdp {
@@ -45,16 +46,30 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   return v;
 }
 
-template <bool LS, bool TK>
+// MIX (a second target per row, tgt_b, and a device-side weight lam[0]: mixup / CutMix):
+//   loss = lam CE_eps(z, t_a) + (1 - lam) CE_eps(z, t_b)
+//        = logsumexp(z) - (1 - eps) (lam z_ta + (1 - lam) z_tb) - (eps / C) sum_c z_c
+// in the same max-relative form; either target out of range poisons the loss. No correct count.
+template <bool LS>
+__device__ __forceinline__ float xent_mix_row(float lse_rel, float mx, float zta, float ztb, float lam, float sz,
+                                              float eps, int C) {
+  const float d = lam * (mx - zta) + (1.f - lam) * (mx - ztb);
+  return LS ? lse_rel + (1.f - eps) * d - (eps / (float)C) * sz : lse_rel + d;
+}
+
+template <bool LS, bool TK, bool MIX>
 __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ tgt,
                                                        int B, int C, float* __restrict__ loss,
                                                        long long* __restrict__ correct, float* __restrict__ sum_out,
-                                                       float eps, int topk) {
+                                                       float eps, int topk, const long long* __restrict__ tgt_b,
+                                                       const float* __restrict__ lam_p) {
   __shared__ double red[16];
   __shared__ int redc[16];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   double acc = 0.0;
   int nc = 0;
+  float lam = 1.f;
+  if (MIX) lam = lam_p[0];
   if (C <= 64) {
     for (int r = tid; r < B; r += 1024) {
       const float* row = logits + (long long)r * C;
@@ -68,7 +83,14 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
       for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
       const long long t = tgt[r];
       const bool tok = t >= 0 && t < C;  // out-of-range targets poison the loss instead of reading OOB
-      if (LS) {
+      if (MIX) {
+        const long long tb = tgt_b[r];
+        const bool ok = tok && tb >= 0 && tb < C;
+        float sz = 0.f;
+        if (LS)
+          for (int c = 0; c < C; ++c) sz += row[c] - mx;
+        acc += ok ? (double)xent_mix_row<LS>(logf(se), mx, row[t], row[tb], lam, sz, eps, C) : (double)NAN;
+      } else if (LS) {
         float sz = 0.f;
         for (int c = 0; c < C; ++c) sz += row[c] - mx;
         acc += tok ? (double)xent_ls_row(logf(se), mx, row[t], sz, eps, C) : (double)NAN;
@@ -147,7 +169,12 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
         if (lane == 0) {
           const long long t = tgt[r];
           const bool tok = t >= 0 && t < C;
-          if (LS)
+          if (MIX) {
+            const long long tb = tgt_b[r];
+            const float* zr = logits + (long long)r * C;
+            acc += (tok && tb >= 0 && tb < C) ? (double)xent_mix_row<LS>(logf(se), mx, zr[t], zr[tb], lam, sz, eps, C)
+                                              : (double)NAN;
+          } else if (LS)
             acc += tok ? (double)xent_ls_row(logf(se), mx, logits[(long long)r * C + t], sz, eps, C) : (double)NAN;
           else
             acc += tok ? (double)(logf(se) + mx - logits[(long long)r * C + t]) : (double)NAN;
@@ -196,7 +223,11 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
       if (lane == 0) {
         const long long t = tgt[r];
         const bool tok = t >= 0 && t < C;
-        if (LS)
+        if (MIX) {
+          const long long tb = tgt_b[r];
+          acc += (tok && tb >= 0 && tb < C) ? (double)xent_mix_row<LS>(logf(se), mx, row[t], row[tb], lam, sz, eps, C)
+                                            : (double)NAN;
+        } else if (LS)
           acc += tok ? (double)xent_ls_row(logf(se), mx, row[t], sz, eps, C) : (double)NAN;
         else
           acc += tok ? (double)(logf(se) + mx - row[t]) : (double)NAN;
@@ -229,10 +260,28 @@ __global__ __launch_bounds__(1024) void xent_fwd_kernel(const float* __restrict_
 }
 
 // dlogits = (softmax - onehot) * gscale[0] / B; LS: (softmax - (1 - eps) onehot - eps / C) * gscale[0] / B
-template <bool LS>
+// MIX: dlogits = (softmax - (1 - eps) (lam onehot_a + (1 - lam) onehot_b) - eps / C) * gscale[0] / B, for every
+// eps (0 included); with t_a == t_b the two one-hot weights add on the same class. Each step is rounded
+// on its own (no contraction), so xent_bwd_kernel and xent_linear_bwd_kernel give the same bits.
+struct XentMixW {
+  float wa, wb, off;
+};
+__device__ __forceinline__ XentMixW xent_mix_w(float lam, float eps, int C) {
+  const float on = 1.f - eps;
+  return XentMixW{on * lam, on * (1.f - lam), eps / (float)C};
+}
+__device__ __forceinline__ float xent_mix_grad(float e, float inv, bool isa, bool isb, const XentMixW& w, float k) {
+  const float sm = __fmul_rn(e, inv);
+  const float tw = __fadd_rn(isa ? w.wa : 0.f, isb ? w.wb : 0.f);
+  return __fmul_rn(__fsub_rn(__fsub_rn(sm, tw), w.off), k);
+}
+
+template <bool LS, bool MIX>
 __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ tgt,
                                                       const float* __restrict__ gscale, int B, int C,
-                                                      float* __restrict__ dlogits, float eps) {
+                                                      float* __restrict__ dlogits, float eps,
+                                                      const long long* __restrict__ tgt_b,
+                                                      const float* __restrict__ lam_p) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= B) return;
@@ -247,6 +296,13 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
   const float inv = 1.f / se;
   const long long t = tgt[r];
   const float on = 1.f - eps, off = eps / (float)C;  // (LS only)
+  if (MIX) {
+    const long long tb = tgt_b[r];
+    const XentMixW mw = xent_mix_w(lam_p[0], eps, C);
+    for (int c = lane; c < C; c += 64)
+      dlogits[(long long)r * C + c] = xent_mix_grad(expf(row[c] - mx), inv, c == t, c == tb, mw, k);
+    return;
+  }
   for (int c = lane; c < C; c += 64) {
     const float sm = expf(row[c] - mx) * inv;
     if (LS)
@@ -580,6 +636,41 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
 // out[b][h][w][c] (NHWC fp32) from uint8 HWC images[idx[b]], with optional RandomCrop(pad) and
 // RandomHorizontalFlip(0.5) drawn from a counter-based hash of (seed, *counter, b), then
 // ToTensor (/255) and Normalize(mean, std). Padding is zero in uint8 space (torchvision fill=0).
+struct AugImage {
+  const unsigned char* src;
+  int oy, ox;
+  bool fl;
+};
+// image b of the batch: its source and its own crop / flip draws
+__device__ __forceinline__ AugImage aug_image(const unsigned char* __restrict__ imgs, long long src_i, int H, int W,
+                                              int C, int pad, int flip, unsigned long long seed,
+                                              unsigned long long ctr, int b) {
+  const unsigned long long r = splitmix64(seed ^ splitmix64(ctr * 0x100000001B3ull + (unsigned long long)b));
+  const int span = 2 * pad + 1;
+  AugImage a;
+  a.oy = pad ? (int)(r % span) - pad : 0;
+  a.ox = pad ? (int)((r >> 16) % span) - pad : 0;
+  a.fl = flip && ((r >> 40) & 1);
+  a.src = imgs + src_i * (long long)H * W * C;
+  return a;
+}
+// channel c of output pixel (h, w) of such an image, normalised
+__device__ __forceinline__ const unsigned char* aug_pixel(const AugImage& a, int h, int w, int H, int W, int C,
+                                                          bool& in) {
+  const int ww = a.fl ? (W - 1 - w) : w;  // flip applied after the crop (torchvision order)
+  const int sh = h + a.oy, sw = ww + a.ox;
+  in = (unsigned)sh < (unsigned)H && (unsigned)sw < (unsigned)W;
+  return a.src + (long long)(in ? sh * W + sw : 0) * C;
+}
+
+// MIX (mixup / CutMix on, see mix.h): image b is paired with p = B - 1 - b (batch reversal); every
+// workgroup evaluates the batch's mix parameters itself, workgroup (0, 0) publishes them in mix[8].
+// With X the batch this kernel writes without MIX at the same seed and counter:
+//   mixup   out[b] = lam X[b] + (1 - lam) X[p]
+//   cutmix  out[b] = X[p] inside the box, X[b] outside (bitwise)
+//   none    out[b] = X[b] (bitwise; the partner image is not read)
+// and labels_b[b] = labels of image p. The partner's crop and flip are its own draws (hashed with p).
+template <bool MIX>
 __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __restrict__ imgs,
                                                      const long long* __restrict__ idx, long long idx_off, int B,
                                                      int H, int W, int C, float m0, float m1, float m2, float is0,
@@ -587,7 +678,8 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
                                                      const long long* __restrict__ counter, unsigned long long seed,
                                                      float* __restrict__ out, long long nbatches,
                                                      const long long* __restrict__ labels,
-                                                     long long* __restrict__ labels_out) {
+                                                     long long* __restrict__ labels_out, MixCfg cfg,
+                                                     float* __restrict__ mix, long long* __restrict__ labels_b) {
   const int b = blockIdx.y;
   if (b >= B) return;
   const unsigned long long ctr = counter ? (unsigned long long)counter[0] : 0ull;
@@ -596,29 +688,79 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
   const long long off = nbatches > 0 ? idx_off + (long long)(ctr % (unsigned long long)nbatches) * B : idx_off;
   const long long src_i = idx ? idx[off + b] : (off + b);
   if (labels_out && blockIdx.x == 0 && threadIdx.x == 0) labels_out[b] = labels[src_i];
-  const unsigned long long r = splitmix64(seed ^ splitmix64(ctr * 0x100000001B3ull + (unsigned long long)b));
-  const int span = 2 * pad + 1;
-  const int oy = pad ? (int)(r % span) - pad : 0;
-  const int ox = pad ? (int)((r >> 16) % span) - pad : 0;
-  const bool fl = flip && ((r >> 40) & 1);
-  const unsigned char* src = imgs + src_i * (long long)H * W * C;
+  const AugImage ia = aug_image(imgs, src_i, H, W, C, pad, flip, seed, ctr, b);
   const float mean[3] = {m0, m1, m2};
   const float istd[3] = {is0, is1, is2};
   const int npix = H * W;
   float* dst = out + (long long)b * npix * C;
-  // one thread per output pixel, all its channels (one index decode per pixel, not per element)
+  if (!MIX) {
+    // one thread per output pixel, all its channels (one index decode per pixel, not per element)
+    for (int px = blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += gridDim.x * blockDim.x) {
+      const int h = px / W, w = px - (px / W) * W;
+      bool in;
+      const unsigned char* sp = aug_pixel(ia, h, w, H, W, C, in);
+      for (int c = 0; c < C; ++c) {
+        const float v = in ? (float)sp[c] * (1.f / 255.f) : 0.f;
+        const int ci = c < 3 ? c : 2;
+        dst[(long long)px * C + c] = (v - mean[ci]) * istd[ci];
+      }
+    }
+    return;
+  }
+  const MixParams mp = mix_draw(seed, ctr, cfg, H, W);
+  const int p = B - 1 - b;
+  const long long src_p = idx ? idx[off + p] : (off + p);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (labels_b) labels_b[b] = labels[src_p];
+    if (b == 0 && mix) mix_publish(mix, mp);
+  }
+  const AugImage ib = aug_image(imgs, src_p, H, W, C, pad, flip, seed, ctr, p);
+  // The mode is uniform over the grid: mixup reads both images; CutMix and none read one source per
+  // pixel, in the unmixed kernel's loop.
+  if (mp.mode == kMixMixup) {
+    const float lam = mp.lam, oml = 1.f - mp.lam;
+    for (int px = blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += gridDim.x * blockDim.x) {
+      const int h = px / W, w = px - (px / W) * W;
+      bool ina, inb;
+      const unsigned char* spa = aug_pixel(ia, h, w, H, W, C, ina);
+      const unsigned char* spb = aug_pixel(ib, h, w, H, W, C, inb);
+      for (int c = 0; c < C; ++c) {
+        const float va = ina ? (float)spa[c] * (1.f / 255.f) : 0.f;
+        const float vb = inb ? (float)spb[c] * (1.f / 255.f) : 0.f;
+        const int ci = c < 3 ? c : 2;
+        const float xa = (va - mean[ci]) * istd[ci], xb = (vb - mean[ci]) * istd[ci];
+        dst[(long long)px * C + c] = lam * xa + oml * xb;
+      }
+    }
+    return;
+  }
+  const bool cut = mp.mode == kMixCutmix;
   for (int px = blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += gridDim.x * blockDim.x) {
     const int h = px / W, w = px - (px / W) * W;
-    const int ww = fl ? (W - 1 - w) : w;  // flip applied after the crop (torchvision order)
-    const int sh = h + oy, sw = ww + ox;
-    const bool in = (unsigned)sh < (unsigned)H && (unsigned)sw < (unsigned)W;
-    const unsigned char* sp = src + (long long)(in ? sh * W + sw : 0) * C;
+    // CutMix: the pixel comes whole from the partner inside the box, from the image itself outside
+    const bool box = cut && h >= mp.y0 && h < mp.y1 && w >= mp.x0 && w < mp.x1;
+    AugImage s;
+    s.src = box ? ib.src : ia.src;
+    s.oy = box ? ib.oy : ia.oy;
+    s.ox = box ? ib.ox : ia.ox;
+    s.fl = box ? ib.fl : ia.fl;
+    bool in;
+    const unsigned char* sp = aug_pixel(s, h, w, H, W, C, in);
     for (int c = 0; c < C; ++c) {
       const float v = in ? (float)sp[c] * (1.f / 255.f) : 0.f;
       const int ci = c < 3 ? c : 2;
       dst[(long long)px * C + c] = (v - mean[ci]) * istd[ci];
     }
   }
+}
+
+// mix[i] = the published row of step counter first + i: mix_draw over n consecutive counters (the
+// schedule a loader will follow, for logging and for the distribution tests)
+__global__ __launch_bounds__(256) void mix_params_kernel(unsigned long long seed, long long first, long long n,
+                                                        MixCfg cfg, int H, int W, float* __restrict__ mix) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  mix_publish(mix + i * kMixRow, mix_draw(seed, (unsigned long long)(first + i), cfg, H, W));
 }
 
 __global__ void counter_inc_kernel(long long* c) { c[0] += 1; }
@@ -908,7 +1050,9 @@ __global__ __launch_bounds__(256) void small_linear_bwd_kernel(const float* __re
 // Three launches (xent_bwd, small_linear_bwd, bn_bwd_reduce) and two kernel boundaries less per step.
 // LS (label smoothing eps > 0): dlogits = (softmax - (1 - eps) onehot(t) - eps / O) * gscale / B, as
 // xent_bwd_kernel<true>; the sdy tile then carries the smoothed gradient and nothing else differs.
-template <bool LS>
+// MIX (tgt_b, lam: xent_bwd_kernel<., true>'s gradient, bit for bit, for every eps): the butterfly sum
+// order whatever eps is, and xent_mix_grad's rounding steps.
+template <bool LS, bool MIX>
 __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __restrict__ logits,
                                                               const long long* __restrict__ tgt,
                                                               const float* __restrict__ gscale,
@@ -916,10 +1060,13 @@ __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __res
                                                               int B, int I, int O, float* __restrict__ dlogits,
                                                               float* __restrict__ dx, float* __restrict__ dw,
                                                               float* __restrict__ db, int nbx, int nbw, XentBnLink lk,
-                                                              float eps) {
+                                                              float eps, const long long* __restrict__ tgt_b,
+                                                              const float* __restrict__ lam_p) {
   __shared__ float sdy[kXentLinMax];
   const float k = gscale[0] / (float)B;
   const float on = 1.f - eps, off = eps / (float)O;  // (LS only)
+  XentMixW mw{0.f, 0.f, 0.f};
+  if (MIX) mw = xent_mix_w(lam_p[0], eps, O);
   for (int r = threadIdx.x; r < B; r += 256) {
     const float* row = logits + (long long)r * O;
     float v[SL_MAXO];
@@ -930,7 +1077,7 @@ __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __res
       mx = fmaxf(mx, v[o]);
     }
     float se = 0.f;
-    if (LS) {
+    if (LS || MIX) {
       // the sum in the order of xent_bwd_kernel's wave_sum (a xor butterfly over the lanes o < 16;
       // o >= O adds exact zeros): the smoothed gradient of the fused and of the unfused classifier
       // backward are then the same bits. (The plain sum below differs from that kernel's by an ulp.)
@@ -951,11 +1098,14 @@ __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __res
     }
     const float inv = 1.f / se;
     const long long t = tgt[r];
+    long long tb = -1;
+    if (MIX) tb = tgt_b[r];
 #pragma unroll
     for (int o = 0; o < SL_MAXO; ++o) {
       if (o >= O) break;
-      const float d = LS ? (expf(v[o] - mx) * inv - (o == t ? on : 0.f) - off) * k
-                         : (expf(v[o] - mx) * inv - (o == t ? 1.f : 0.f)) * k;
+      const float d = MIX  ? xent_mix_grad(expf(v[o] - mx), inv, o == t, o == tb, mw, k)
+                      : LS ? (expf(v[o] - mx) * inv - (o == t ? on : 0.f) - off) * k
+                           : (expf(v[o] - mx) * inv - (o == t ? 1.f : 0.f)) * k;
       sdy[r * O + o] = d;
       if (blockIdx.x == 0) dlogits[(long long)r * O + o] = d;
     }
@@ -1164,19 +1314,30 @@ __global__ __launch_bounds__(256) void wtrans_sub_kernel(const float* __restrict
 }  // namespace
 
 void xent_fwd_launch(const float* logits, const long long* tgt, int B, int C, float* loss, long long* correct,
-                     float* sum_out, hipStream_t st, float eps, int topk) {
+                     float* sum_out, hipStream_t st, float eps, int topk, const long long* tgt_b, const float* lam) {
   if (!(eps >= 0.f && eps <= 1.f) || topk < 1) throw std::runtime_error("xent_fwd: label smoothing in [0, 1], topk >= 1");
+  if ((tgt_b != nullptr) != (lam != nullptr)) throw std::runtime_error("xent_fwd: tgt_b and lam go together");
   // eps == 0 and topk == 1 take the plain instantiation: the arithmetic of a call without them
   const bool ls = eps != 0.f, tk = topk > 1;
-  auto kern = ls ? (tk ? xent_fwd_kernel<true, true> : xent_fwd_kernel<true, false>)
-                 : (tk ? xent_fwd_kernel<false, true> : xent_fwd_kernel<false, false>);
-  hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, st, logits, tgt, B, C, loss, correct, sum_out, eps, topk);
+  if (tgt_b) {
+    if (correct || tk) throw std::runtime_error("xent_fwd: no correct count with a second target");
+    auto kern = ls ? xent_fwd_kernel<true, false, true> : xent_fwd_kernel<false, false, true>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, st, logits, tgt, B, C, loss, correct, sum_out, eps, topk, tgt_b,
+                       lam);
+    return;
+  }
+  auto kern = ls ? (tk ? xent_fwd_kernel<true, true, false> : xent_fwd_kernel<true, false, false>)
+                 : (tk ? xent_fwd_kernel<false, true, false> : xent_fwd_kernel<false, false, false>);
+  hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, st, logits, tgt, B, C, loss, correct, sum_out, eps, topk, tgt_b,
+                     lam);
 }
 void xent_bwd_launch(const float* logits, const long long* tgt, const float* gscale, int B, int C, float* dlogits,
-                     hipStream_t st, float eps) {
+                     hipStream_t st, float eps, const long long* tgt_b, const float* lam) {
   if (!(eps >= 0.f && eps <= 1.f)) throw std::runtime_error("xent_bwd: label smoothing in [0, 1]");
-  auto kern = eps != 0.f ? xent_bwd_kernel<true> : xent_bwd_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, st, logits, tgt, gscale, B, C, dlogits, eps);
+  if ((tgt_b != nullptr) != (lam != nullptr)) throw std::runtime_error("xent_bwd: tgt_b and lam go together");
+  auto kern = tgt_b ? (eps != 0.f ? xent_bwd_kernel<true, true> : xent_bwd_kernel<false, true>)
+                    : (eps != 0.f ? xent_bwd_kernel<true, false> : xent_bwd_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, st, logits, tgt, gscale, B, C, dlogits, eps, tgt_b, lam);
 }
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
@@ -1220,11 +1381,29 @@ void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* seg
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,
                     unsigned long long seed, float* out, hipStream_t st, long long nbatches,
-                    const long long* labels, long long* labels_out) {
+                    const long long* labels, long long* labels_out, const MixCfg& cfg, float* mix,
+                    long long* labels_b) {
   dim3 grid((H * W + 255) / 256, B);
-  hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, st, imgs, idx, idx_off, B, H, W, C, mean[0], mean[1],
-                     mean[2], inv_std[0], inv_std[1], inv_std[2], pad, flip ? 1 : 0, counter, seed, out, nbatches,
-                     labels, labels_out);
+  // both alphas 0: the instantiation without mixing, whose output does not depend on cfg
+  const bool mixing = mix_enabled(cfg);
+  if (mixing && (!mix || (labels_b && !labels)))
+    throw std::runtime_error("augment: mixing needs the mix row (and labels for labels_b)");
+  if (!(cfg.mixup_alpha >= 0.f && cfg.cutmix_alpha >= 0.f && cfg.prob >= 0.f && cfg.prob <= 1.f &&
+        cfg.switch_prob >= 0.f && cfg.switch_prob <= 1.f))
+    throw std::runtime_error("augment: mix alphas >= 0 and probabilities in [0, 1]");
+  auto kern = mixing ? augment_kernel<true> : augment_kernel<false>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, imgs, idx, idx_off, B, H, W, C, mean[0], mean[1], mean[2],
+                     inv_std[0], inv_std[1], inv_std[2], pad, flip ? 1 : 0, counter, seed, out, nbatches, labels,
+                     labels_out, cfg, mix, labels_b);
+}
+void mix_params_launch(unsigned long long seed, long long first, long long n, const MixCfg& cfg, int H, int W,
+                       float* mix, hipStream_t st) {
+  if (n <= 0) return;
+  if (!(cfg.mixup_alpha >= 0.f && cfg.cutmix_alpha >= 0.f && cfg.prob >= 0.f && cfg.prob <= 1.f &&
+        cfg.switch_prob >= 0.f && cfg.switch_prob <= 1.f) || H < 1 || W < 1)
+    throw std::runtime_error("mix_params: mix alphas >= 0, probabilities in [0, 1], H, W >= 1");
+  hipLaunchKernelGGL(mix_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, seed, first, n, cfg, H, W,
+                     mix);
 }
 void subpixel_zero_launch(float* dx, int N, int H, int W, int C, int mask, hipStream_t st) {
   if ((long long)N * H * W >= (1LL << 31) || (C & 3)) throw std::runtime_error("subpixel_zero: bad shape");
@@ -1344,15 +1523,18 @@ void small_linear_bwd_launch(const float* dy, const float* x, const float* w, in
 }
 void xent_linear_bwd_launch(const float* logits, const long long* tgt, const float* gscale, const float* x,
                             const float* w, int B, int I, int O, float* dlogits, float* dx, float* dw, float* db,
-                            const XentBnLink& lk, hipStream_t st, float eps) {
+                            const XentBnLink& lk, hipStream_t st, float eps, const long long* tgt_b,
+                            const float* lam) {
   if (O > SL_MAXO || (long long)B * O > kXentLinMax) throw std::runtime_error("xent_linear_bwd: classifier too wide");
   if (lk.y && (!dx || lk.ps < 2 || lk.ps > 3)) throw std::runtime_error("xent_linear_bwd: BN link needs dX");
   if (!(eps >= 0.f && eps <= 1.f)) throw std::runtime_error("xent_linear_bwd: label smoothing in [0, 1]");
   const int nbx = dx ? ((I + 15) / 16) * xent_lin_chunks(B) : 0;
   const int nbw = (I + 15) / 16;
-  auto kern = eps != 0.f ? xent_linear_bwd_kernel<true> : xent_linear_bwd_kernel<false>;
+  if ((tgt_b != nullptr) != (lam != nullptr)) throw std::runtime_error("xent_linear_bwd: tgt_b and lam go together");
+  auto kern = tgt_b ? (eps != 0.f ? xent_linear_bwd_kernel<true, true> : xent_linear_bwd_kernel<false, true>)
+                    : (eps != 0.f ? xent_linear_bwd_kernel<true, false> : xent_linear_bwd_kernel<false, false>);
   hipLaunchKernelGGL(kern, dim3(nbx + nbw + 1), dim3(256), 0, st, logits, tgt, gscale, x, w, B, I, O, dlogits, dx, dw,
-                     db, nbx, nbw, lk, eps);
+                     db, nbx, nbw, lk, eps, tgt_b, lam);
 }
 void avgpool_fwd_launch(const float* x, int N, int HW, int C, float* y, hipStream_t st) {
   if ((long long)N * HW * C >= (1LL << 31)) throw std::runtime_error("avgpool: tensor too large");

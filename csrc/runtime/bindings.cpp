@@ -84,15 +84,17 @@ PYBIND11_MODULE(_C, m) {
   m.def("linear_bwd", &linear_bwd, py::arg("gy"), py::arg("x"), py::arg("w"), py::arg("need_dx"),
         py::arg("has_bias"), py::arg("dw_out") = py::none(), py::arg("db_out") = py::none());
   m.def("xent_fwd", &xent_fwd, py::arg("logits"), py::arg("target"), py::arg("correct") = py::none(),
-        py::arg("label_smoothing") = 0.0, py::arg("topk") = 1);
-  m.def("xent_bwd", &xent_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("label_smoothing") = 0.0);
+        py::arg("label_smoothing") = 0.0, py::arg("topk") = 1, py::arg("target_b") = py::none(),
+        py::arg("lam") = py::none());
+  m.def("xent_bwd", &xent_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("label_smoothing") = 0.0,
+        py::arg("target_b") = py::none(), py::arg("lam") = py::none());
   m.def("gemm_log", &gemm_log, py::arg("clear") = false,
         "CDP_GEMM_LOG=1: (kind, M, N, K, bm, bn, splits) of every conv / weight-gradient GEMM launch so far");
   m.def("xent_linear_bwd", &xent_linear_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("x"),
         py::arg("w"), py::arg("need_dx"), py::arg("has_bias"), py::arg("dw_out") = py::none(),
         py::arg("db_out") = py::none(), py::arg("link_y") = py::none(), py::arg("link_stats") = py::none(),
         py::arg("link_pool") = false, py::arg("link_relu") = false, py::arg("link_ps") = 2,
-        py::arg("label_smoothing") = 0.0,
+        py::arg("label_smoothing") = 0.0, py::arg("target_b") = py::none(), py::arg("lam") = py::none(),
         "CrossEntropy backward + narrow Linear backward in one launch (+ the BN backward partials of the block "
         "that produced the Linear's input, link_*): {dlogits, dx, dw, db, part}");
   py::class_<LarsStep>(m, "LarsStep", "the LARS block of sgd_step / sgd_step_prep (default: off)")
@@ -138,9 +140,17 @@ PYBIND11_MODULE(_C, m) {
   m.def("augment", &augment, py::arg("images"), py::arg("indices"), py::arg("idx_offset"), py::arg("batch"),
         py::arg("mean"), py::arg("std"), py::arg("pad"), py::arg("flip"), py::arg("counter"), py::arg("seed"),
         py::arg("out") = py::none(), py::arg("nbatches") = 0, py::arg("labels") = py::none(),
-        py::arg("labels_out") = py::none(),
+        py::arg("labels_out") = py::none(), py::arg("mixup_alpha") = 0.0, py::arg("cutmix_alpha") = 0.0,
+        py::arg("mix_prob") = 1.0, py::arg("mix_switch_prob") = 0.5, py::arg("mix") = py::none(),
+        py::arg("labels_b") = py::none(),
         "gather + RandomCrop + flip + normalize one batch (NHWC fp32); nbatches > 0 takes the batch offset from "
-        "the step counter; labels_out receives the batch's labels");
+        "the step counter; labels_out receives the batch's labels; an alpha > 0 mixes image b with image "
+        "batch - 1 - b (mixup / CutMix), publishing {mode, lam, lam_raw, y0, y1, x0, x1, 0} in mix and the "
+        "partners' labels in labels_b");
+  m.def("mix_params", &mix_params, py::arg("seed"), py::arg("first_counter"), py::arg("n"),
+        py::arg("mixup_alpha") = 0.0, py::arg("cutmix_alpha") = 0.0, py::arg("mix_prob") = 1.0,
+        py::arg("mix_switch_prob") = 0.5, py::arg("H") = 32, py::arg("W") = 32,
+        "float32 [n, 8]: the mix rows augment publishes at step counters first_counter .. first_counter + n - 1");
   m.def("counter_inc", &counter_inc);
   m.def("stack_mean", &stack_mean);
   m.def("scale_", &scale_);

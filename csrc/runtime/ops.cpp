@@ -1812,8 +1812,36 @@ std::vector<at::Tensor> linear_bwd(const at::Tensor& gy_, const at::Tensor& x_, 
 // {loss (0-dim), correct (int64 [1], accumulated in place when given)}
 // label_smoothing eps: loss against (1 - eps) onehot + eps / C; topk: a row is correct when fewer than
 // topk logits rank above its target's (ties to the lower index)
+// target_b, lam (mixup / CutMix; both or neither): a second int64 target per row and a 1-element fp32 device
+// weight, loss = lam CE(z, target) + (1 - lam) CE(z, target_b). The kernels read lam from the device.
+namespace {
+struct MixPair {
+  at::Tensor tb, lam;  // (kept alive over the launch)
+  const long long* tbp = nullptr;
+  const float* lamp = nullptr;
+};
+MixPair mix_pair(const c10::optional<at::Tensor>& target_b, const c10::optional<at::Tensor>& lam,
+                 const at::Tensor& logits, const char* op) {
+  MixPair m;
+  const bool hb = target_b.has_value() && target_b->defined(), hl = lam.has_value() && lam->defined();
+  TORCH_CHECK(hb == hl, op, ": target_b and lam must be given together");
+  if (!hb) return m;
+  TORCH_CHECK(target_b->scalar_type() == at::kLong && target_b->numel() == logits.size(0) &&
+                  target_b->device() == logits.device(),
+              op, ": target_b must be int64, one per row, on the logits' device");
+  TORCH_CHECK(lam->scalar_type() == at::kFloat && lam->numel() == 1 && lam->device() == logits.device(),
+              op, ": lam must be a 1-element float32 tensor on the logits' device");
+  m.tb = target_b->contiguous();
+  m.lam = *lam;
+  m.tbp = reinterpret_cast<const long long*>(m.tb.data_ptr<int64_t>());
+  m.lamp = m.lam.data_ptr<float>();
+  return m;
+}
+}  // namespace
+
 at::Tensor xent_fwd(const at::Tensor& logits_, const at::Tensor& target, const c10::optional<at::Tensor>& correct,
-                    double label_smoothing, int64_t topk) {
+                    double label_smoothing, int64_t topk, const c10::optional<at::Tensor>& target_b,
+                    const c10::optional<at::Tensor>& lam) {
   check_f32_cuda(logits_, "logits");
   TORCH_CHECK(target.scalar_type() == at::kLong, "target must be int64");
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent_fwd: label_smoothing must be in [0, 1], got ",
@@ -1825,21 +1853,26 @@ at::Tensor xent_fwd(const at::Tensor& logits_, const at::Tensor& target, const c
   at::Tensor loss = at::empty({}, logits.options());
   long long* cp = nullptr;
   if (correct.has_value() && correct->defined()) cp = reinterpret_cast<long long*>(correct->data_ptr<int64_t>());
+  TORCH_CHECK(tgt.numel() == B, "xent_fwd: one target per row");
+  const MixPair mp = mix_pair(target_b, lam, logits, "xent_fwd");
+  TORCH_CHECK(!(mp.tbp && (cp || topk > 1)), "xent_fwd: the correct count is not offered together with target_b");
   xent_fwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(tgt.data_ptr<int64_t>()), B, C, loss.data_ptr<float>(), cp, nullptr,
-                  cur_stream(), (float)label_smoothing, (int)std::min<int64_t>(topk, 0x7fffffff));
+                  cur_stream(), (float)label_smoothing, (int)std::min<int64_t>(topk, 0x7fffffff), mp.tbp, mp.lamp);
   return loss;
 }
 
 at::Tensor xent_bwd(const at::Tensor& gloss, const at::Tensor& logits_, const at::Tensor& target,
-                    double label_smoothing) {
+                    double label_smoothing, const c10::optional<at::Tensor>& target_b,
+                    const c10::optional<at::Tensor>& lam) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "xent_bwd: label_smoothing must be in [0, 1], got ",
               label_smoothing);
   const at::Tensor logits = logits_.contiguous();
   const at::Tensor g = gloss.to(at::kFloat).contiguous();
   const int B = logits.size(0), C = logits.size(1);
   at::Tensor d = at::empty_like(logits);
+  const MixPair mp = mix_pair(target_b, lam, logits, "xent_bwd");
   xent_bwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(target.contiguous().data_ptr<int64_t>()), g.data_ptr<float>(), B, C,
-                  d.data_ptr<float>(), cur_stream(), (float)label_smoothing);
+                  d.data_ptr<float>(), cur_stream(), (float)label_smoothing, mp.tbp, mp.lamp);
   return d;
 }
 
@@ -1851,7 +1884,9 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
                                         const c10::optional<at::Tensor>& dw_out, const c10::optional<at::Tensor>& db_out,
                                         const c10::optional<at::Tensor>& link_y,
                                         const c10::optional<at::Tensor>& link_stats, bool link_pool, bool link_relu,
-                                        int64_t link_ps, double label_smoothing) {
+                                        int64_t link_ps, double label_smoothing,
+                                        const c10::optional<at::Tensor>& target_b,
+                                        const c10::optional<at::Tensor>& lam) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0,
               "xent_linear_bwd: label_smoothing must be in [0, 1], got ", label_smoothing);
   const at::Tensor logits = logits_.contiguous(), x = x_.contiguous(), w = w_.contiguous();
@@ -1863,6 +1898,7 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
   TORCH_CHECK(logits.size(0) == B && logits.size(1) == O && w.size(1) == I, "xent_linear_bwd: shape mismatch");
   TORCH_CHECK(O <= 16 && (long long)B * O <= kXentLinMax, "xent_linear_bwd: classifier too wide");
   TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == B, "xent_linear_bwd: int64 target per row");
+  const MixPair mp = mix_pair(target_b, lam, logits, "xent_linear_bwd");
   at::Tensor dl = at::empty_like(logits);
   at::Tensor dx = need_dx ? at::empty({B, I}, x.options()) : at::Tensor();
   at::Tensor dw = (dw_out.has_value() && dw_out->defined()) ? *dw_out : at::empty({O, I}, x.options());
@@ -1889,7 +1925,8 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
   xent_linear_bwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(tgt.data_ptr<int64_t>()),
                          g.data_ptr<float>(), x.data_ptr<float>(), w.data_ptr<float>(), B, I, O, dl.data_ptr<float>(),
                          need_dx ? dx.data_ptr<float>() : nullptr, dw.data_ptr<float>(),
-                         has_bias ? db.data_ptr<float>() : nullptr, lk, cur_stream(), (float)label_smoothing);
+                         has_bias ? db.data_ptr<float>() : nullptr, lk, cur_stream(), (float)label_smoothing, mp.tbp,
+                         mp.lamp);
   return {dl, dx, dw, db, part};
 }
 
@@ -2268,11 +2305,21 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
 }
 
 // ---------------------------------------------------------------- data augmentation
+namespace {
+MixCfg mix_cfg(double mixup_alpha, double cutmix_alpha, double prob, double switch_prob, const char* op) {
+  TORCH_CHECK(mixup_alpha >= 0.0 && cutmix_alpha >= 0.0, op, ": mixup_alpha and cutmix_alpha must be >= 0");
+  TORCH_CHECK(prob >= 0.0 && prob <= 1.0 && switch_prob >= 0.0 && switch_prob <= 1.0, op,
+              ": mix_prob and mix_switch_prob must be in [0, 1]");
+  return MixCfg{(float)mixup_alpha, (float)cutmix_alpha, (float)prob, (float)switch_prob};
+}
+}  // namespace
 at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& indices, int64_t idx_offset, int64_t batch,
                    std::vector<double> mean, std::vector<double> std_, int64_t pad, bool flip,
                    const c10::optional<at::Tensor>& counter, int64_t seed, c10::optional<at::Tensor> out,
                    int64_t nbatches, const c10::optional<at::Tensor>& labels,
-                   const c10::optional<at::Tensor>& labels_out) {
+                   const c10::optional<at::Tensor>& labels_out, double mixup_alpha, double cutmix_alpha,
+                   double mix_prob, double mix_switch_prob, const c10::optional<at::Tensor>& mix,
+                   const c10::optional<at::Tensor>& labels_b) {
   TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.dim() == 4,
               "images must be uint8 [N, H, W, C] on the GPU");
   const int H = images.size(1), W = images.size(2), C = images.size(3);
@@ -2315,9 +2362,35 @@ at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& in
     lp = reinterpret_cast<const long long*>(labels->data_ptr<int64_t>());
     lo = reinterpret_cast<long long*>(labels_out->data_ptr<int64_t>());
   }
+  // mixup / CutMix: on with an alpha > 0; then the batch's parameters are published in mix[8] and the
+  // partners' labels (image batch - 1 - b) in labels_b
+  const MixCfg cfg = mix_cfg(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, "augment");
+  float* mixp = nullptr;
+  long long* lb = nullptr;
+  if (mix_enabled(cfg)) {
+    TORCH_CHECK(mix.has_value() && mix->defined() && mix->device() == images.device() &&
+                    mix->scalar_type() == at::kFloat && mix->numel() >= kMixRow && mix->is_contiguous(),
+                "augment: mixing needs mix, a contiguous float32 tensor of 8 on the images' device");
+    mixp = mix->data_ptr<float>();
+    if (labels_b.has_value() && labels_b->defined()) {
+      TORCH_CHECK(lp && labels_b->device() == images.device() && labels_b->scalar_type() == at::kLong &&
+                      labels_b->numel() >= batch && labels_b->is_contiguous(),
+                  "augment: labels_b needs labels / labels_out and must be a contiguous int64 tensor holding the batch");
+      lb = reinterpret_cast<long long*>(labels_b->data_ptr<int64_t>());
+    }
+  }
   augment_launch(images.data_ptr<uint8_t>(), ip, idx_offset, (int)batch, H, W, C, m, is, (int)pad, flip, cp,
-                 (unsigned long long)seed, o.data_ptr<float>(), cur_stream(), nbatches, lp, lo);
+                 (unsigned long long)seed, o.data_ptr<float>(), cur_stream(), nbatches, lp, lo, cfg, mixp, lb);
   return o;
+}
+
+at::Tensor mix_params(int64_t seed, int64_t first_counter, int64_t n, double mixup_alpha, double cutmix_alpha,
+                      double mix_prob, double mix_switch_prob, int64_t H, int64_t W) {
+  TORCH_CHECK(n >= 0 && H >= 1 && W >= 1 && H <= 0x7fff && W <= 0x7fff, "mix_params: n >= 0, 1 <= H, W < 32768");
+  const MixCfg cfg = mix_cfg(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, "mix_params");
+  at::Tensor out = at::empty({n, kMixRow}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA));
+  mix_params_launch((unsigned long long)seed, first_counter, n, cfg, (int)H, (int)W, out.data_ptr<float>(), cur_stream());
+  return out;
 }
 
 void counter_inc(at::Tensor c) { counter_inc_launch(reinterpret_cast<long long*>(c.data_ptr<int64_t>()), cur_stream()); }

@@ -71,17 +71,23 @@ at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
 std::vector<at::Tensor> linear_bwd(const at::Tensor& gy, const at::Tensor& x, const at::Tensor& w, bool need_dx,
                                    bool has_bias, const c10::optional<at::Tensor>& dw_out,
                                    const c10::optional<at::Tensor>& db_out);
+// target_b + lam (both or neither): the two-target loss of mixup / CutMix, lam a 1-element fp32 device tensor
 at::Tensor xent_fwd(const at::Tensor& logits, const at::Tensor& target, const c10::optional<at::Tensor>& correct,
-                    double label_smoothing = 0.0, int64_t topk = 1);
+                    double label_smoothing = 0.0, int64_t topk = 1,
+                    const c10::optional<at::Tensor>& target_b = c10::nullopt,
+                    const c10::optional<at::Tensor>& lam = c10::nullopt);
 at::Tensor xent_bwd(const at::Tensor& gloss, const at::Tensor& logits, const at::Tensor& target,
-                    double label_smoothing = 0.0);
+                    double label_smoothing = 0.0, const c10::optional<at::Tensor>& target_b = c10::nullopt,
+                    const c10::optional<at::Tensor>& lam = c10::nullopt);
 std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tensor& logits, const at::Tensor& target,
                                         const at::Tensor& x, const at::Tensor& w, bool need_dx, bool has_bias,
                                         const c10::optional<at::Tensor>& dw_out, const c10::optional<at::Tensor>& db_out,
                                         const c10::optional<at::Tensor>& link_y = c10::nullopt,
                                         const c10::optional<at::Tensor>& link_stats = c10::nullopt,
                                         bool link_pool = false, bool link_relu = false, int64_t link_ps = 2,
-                                        double label_smoothing = 0.0);
+                                        double label_smoothing = 0.0,
+                                        const c10::optional<at::Tensor>& target_b = c10::nullopt,
+                                        const c10::optional<at::Tensor>& lam = c10::nullopt);
 // The LARS block of a fused SGD step (csrc/kernels/lars.h): descriptor, meta and partials from
 // lars_plan, the partials filled by lars_norms just before; ratios: one float per parameter.
 // Without a descriptor the step is plain SGD.
@@ -125,7 +131,13 @@ at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& in
                    std::vector<double> mean, std::vector<double> std_, int64_t pad, bool flip,
                    const c10::optional<at::Tensor>& counter, int64_t seed, c10::optional<at::Tensor> out,
                    int64_t nbatches = 0, const c10::optional<at::Tensor>& labels = c10::nullopt,
-                   const c10::optional<at::Tensor>& labels_out = c10::nullopt);
+                   const c10::optional<at::Tensor>& labels_out = c10::nullopt, double mixup_alpha = 0.0,
+                   double cutmix_alpha = 0.0, double mix_prob = 1.0, double mix_switch_prob = 0.5,
+                   const c10::optional<at::Tensor>& mix = c10::nullopt,
+                   const c10::optional<at::Tensor>& labels_b = c10::nullopt);
+// float32 [n, 8]: the rows {mode, lam, lam_raw, y0, y1, x0, x1, 0} augment publishes at counters first_counter + i
+at::Tensor mix_params(int64_t seed, int64_t first_counter, int64_t n, double mixup_alpha, double cutmix_alpha,
+                      double mix_prob, double mix_switch_prob, int64_t H, int64_t W);
 void counter_inc(at::Tensor c);
 void stack_mean(const std::vector<at::Tensor>& srcs, at::Tensor dst);
 void gpu_sleep(double us);
