@@ -25,8 +25,18 @@ paths (CPU, ``force_reference``, per-parameter launches) scale it in place as to
 
 :class:`LARS` is the same step with a per-parameter trust ratio (layer-wise adaptive rate scaling, for
 large global batches), derived on the device in the same way from per-parameter sums of squares.
+
+Weight EMA (``ema_decay``): ``e <- d * e + (1 - d) * w`` after every step, in the same launch again: the
+updated weight is in registers, ``e`` (a fourth arena storage, ``state[p]["ema_buffer"]``) is one more
+load and store. ``d`` and ``1 - d`` live on the device (``set_ema_decay``), so a captured step follows
+a decay warm-up without re-capture. A step skipped by ``skip_nonfinite`` leaves ``e`` unchanged, as
+does a step for a parameter without a gradient. ``ema_weights()`` swaps ``e`` into the model for
+evaluation; BatchNorm running statistics are not averaged (they are a moving average already).
 """
 from __future__ import annotations
+
+import contextlib
+import math
 
 import torch
 from torch.optim import Optimizer
@@ -49,6 +59,7 @@ class SGD(Optimizer):
         flat: bool = True,
         max_grad_norm: float | None = None,
         skip_nonfinite: bool = False,
+        ema_decay: float | None = None,
     ):
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -60,6 +71,8 @@ class SGD(Optimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        if ema_decay is not None:
+            _check_ema_decay(ema_decay)
         defaults = dict(
             lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
             maximize=maximize, foreach=None, differentiable=False, fused=None,
@@ -98,6 +111,17 @@ class SGD(Optimizer):
             self._clip_stats = torch.zeros(4, dtype=torch.float32, device=dev)
             if dev.type == "cuda":
                 self._clip_part = torch.zeros(1024, dtype=torch.float64, device=dev)
+        # weight EMA: an optimizer attribute like the clip options; None allocates nothing
+        self._ema_decay = None
+        self._ema_d = self._ema_omd = 0.0  # float32(d), float32(1 - d) as Python floats
+        self._ema_coef = None  # {d, 1 - d} on the device, read by the fused kernels' prologue
+        if ema_decay is not None and all_params:
+            dev = all_params[0].device
+            if dev.type == "cuda":
+                self._ema_coef = torch.zeros(2, dtype=torch.float32, device=dev)  # never inside a capture
+            self._ema_decay = float(ema_decay)
+            self.set_ema_decay(ema_decay)
+            self.reset_ema()
 
     # ------------------------------------------------------------------ gradient clipping
     @property
@@ -168,18 +192,24 @@ class SGD(Optimizer):
         return False
 
     def _on_relayout(self, arena):
-        # the arena moved the momentum values with their parameters; re-point the state views
-        if arena.momentum is None:
-            return
-        views = arena.momentum_views()
-        for p in arena.params:
-            st = self.state.get(p)
-            if st and st.get("momentum_buffer") is not None:
-                st["momentum_buffer"] = views[p._cdp_index]
+        # the arena moved the momentum / EMA values with their parameters; re-point the state views
+        if arena.momentum is not None:
+            views = arena.momentum_views()
+            for p in arena.params:
+                st = self.state.get(p)
+                if st and st.get("momentum_buffer") is not None:
+                    st["momentum_buffer"] = views[p._cdp_index]
+        if self._ema_decay is not None and arena is self._arena and arena.ema is not None:
+            views = arena.ema_views()
+            for p in arena.params:
+                st = self.state.get(p)
+                if st and st.get("ema_buffer") is not None:
+                    st["ema_buffer"] = views[p._cdp_index]
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._adopt_momentum()
+        self._adopt_ema()
 
     def _adopt_momentum(self):
         """Loaded momentum buffers are fresh tensors, while a replayed hipGraph step reads and writes
@@ -196,6 +226,126 @@ class SGD(Optimizer):
                 if b is not None and b.data_ptr() != views[p._cdp_index].data_ptr():
                     views[p._cdp_index].copy_(b)
                     st["momentum_buffer"] = views[p._cdp_index]
+
+    # ------------------------------------------------------------------ weight EMA
+    @property
+    def ema_decay(self):
+        """The EMA decay ``d`` as last set (the host value); None when the EMA is off."""
+        return self._ema_decay
+
+    def set_ema_decay(self, decay: float):
+        """Change the decay of an optimizer built with ``ema_decay``: the two device coefficients are
+        refilled in place, so a captured step uses the new value at its next replay (a decay warm-up
+        without re-capture, as ``lr_tensor`` does for the learning rate). Not while capturing."""
+        if self._ema_decay is None:
+            raise RuntimeError("set_ema_decay: the optimizer was built without ema_decay")
+        _check_ema_decay(decay)
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_ema_decay fills the device coefficients: not while the stream is capturing")
+        d = float(decay)
+        self._ema_decay = d
+        self._ema_d = torch.tensor(d, dtype=torch.float32).item()
+        self._ema_omd = torch.tensor(1.0 - d, dtype=torch.float32).item()  # the subtraction in double
+        if self._ema_coef is not None:
+            self._ema_coef[0:1].fill_(self._ema_d)
+            self._ema_coef[1:2].fill_(self._ema_omd)
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """``e <- w`` for every parameter (e.g. after loading model weights)."""
+        if self._ema_decay is None:
+            raise RuntimeError("reset_ema: the optimizer was built without ema_decay")
+        a = self._arena
+        if a is not None:
+            a.ema_buffer().copy_(a.data)
+            views = a.ema_views()
+        for g in self.param_groups:
+            for p in g["params"]:
+                if a is not None and getattr(p, "_cdp_arena", None) is a:
+                    self.state[p]["ema_buffer"] = views[p._cdp_index]
+                else:
+                    self.state[p]["ema_buffer"] = p.detach().clone(memory_format=torch.preserve_format)
+
+    @torch.no_grad()
+    def _adopt_ema(self):
+        """After ``load_state_dict``: loaded EMA buffers are copied into their arena views (which a
+        replayed step reads and writes), as ``_adopt_momentum`` does; a parameter whose loaded state
+        has none starts again from its current weight."""
+        if self._ema_decay is None:
+            return
+        a = self._arena
+        views = a.ema_views() if a is not None else None
+        for g in self.param_groups:
+            for p in g["params"]:
+                st = self.state[p]
+                b = st.get("ema_buffer")
+                home = views[p._cdp_index] if a is not None and getattr(p, "_cdp_arena", None) is a else None
+                if b is None:
+                    if home is not None:
+                        home.copy_(p.detach())
+                        b = home
+                    else:
+                        b = p.detach().clone(memory_format=torch.preserve_format)
+                elif home is not None and b.data_ptr() != home.data_ptr():
+                    home.copy_(b)
+                    b = home
+                elif home is None:
+                    b = b.detach().clone(memory_format=torch.preserve_format)  # never another optimizer's tensor
+                st["ema_buffer"] = b
+
+    def ema_state(self) -> dict:
+        """``{parameter: its EMA}`` (the live tensors: arena views where the parameters are)."""
+        if self._ema_decay is None:
+            raise RuntimeError("ema_state: the optimizer was built without ema_decay")
+        return {p: self.state[p]["ema_buffer"] for g in self.param_groups for p in g["params"]}
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged weights: the contents of the parameters and of their EMA are
+        exchanged on entry and exchanged back on exit (bitwise, so training continues as if nothing
+        happened). The weight products of the fused step are refreshed (or dropped) both times, since
+        writes through the flat storage bump no parameter version. BatchNorm running statistics are
+        not averaged: the EMA weights evaluate with the live buffers. Not while capturing."""
+        if self._ema_decay is None:
+            raise RuntimeError("ema_weights: the optimizer was built without ema_decay")
+        self._ema_swap()
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+
+    @torch.no_grad()
+    def _ema_swap(self):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ema_weights exchanges the weights with torch ops: not while the stream is capturing")
+        a = self._arena
+        if a is not None:
+            e = a.ema_buffer()
+            tmp = a.data.clone()
+            a.data.copy_(e)
+            e.copy_(tmp)
+            if not a.prep_refresh():
+                a.prep_valid = None
+        for g in self.param_groups:
+            for p in g["params"]:
+                if a is not None and getattr(p, "_cdp_arena", None) is a:
+                    continue
+                e = self.state[p]["ema_buffer"]
+                tmp = p.detach().clone(memory_format=torch.preserve_format)
+                p.copy_(e)  # bumps the version: an eager forward prepares the weight anew
+                e.copy_(tmp)
+
+    def _ema_apply_reference(self, p):
+        """The EMA of one parameter with torch ops, after its update (the arithmetic of the kernels)."""
+        self.state[p]["ema_buffer"].mul_(self._ema_d).add_(p, alpha=self._ema_omd)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if getattr(self, "_ema_decay", None) is not None:  # not the constructor's own calls
+            with torch.no_grad():
+                for p in self.param_groups[-1]["params"]:
+                    self.state[p]["ema_buffer"] = p.detach().clone(memory_format=torch.preserve_format)
+            self._adopt_ema()  # into the arena where the parameter is in it
 
     # ------------------------------------------------------------------ fused weight preparation
     def refresh_weight_prep(self) -> bool:
@@ -301,13 +451,16 @@ class SGD(Optimizer):
         bucket for the reducer's ``set_bucket_step`` -- the SGD of that range, run on the reducer's
         step stream right after the bucket's all-reduce -- or None when the step cannot be split
         this iteration (several param groups, parameters outside one arena run, first and later
-        momentum steps mixed, no native kernels, ``max_grad_norm`` / ``skip_nonfinite`` set). The next ``step()`` then only does the
+        momentum steps mixed, no native kernels, ``max_grad_norm`` / ``skip_nonfinite`` or ``ema_decay``
+        set: the step then runs whole at ``step()``). The next ``step()`` then only does the
         bookkeeping, provided the reducer stepped every bucket; hyperparameters are those at the
         time of this call (the forward), the first-step momentum rule (buf = d_p) is kept."""
         if self._arena is None or len(self.param_groups) != 1 or _native.force_reference():
             return None
         if self._clip_enabled:
             return None  # the clip needs the norm of the whole model: the step runs whole at step()
+        if self._ema_decay is not None:
+            return None  # the per-bucket launches carry no EMA: the step runs whole at step()
         group = self.param_groups[0]
         params, arena = group["params"], self._arena
         if len(params) != len(arena.params) or any(not p.is_cuda for p in params):
@@ -423,19 +576,26 @@ class SGD(Optimizer):
                 buf = torch.empty_like(p, memory_format=torch.contiguous_format)
             pv = p.data if p.data.is_contiguous() else None
             g = p.grad
+            ema = {}
+            eb = st["ema_buffer"] if self._ema_decay is not None else None  # each parameter's own EMA
+            if eb is not None:
+                ec = eb.contiguous()
+                ema = dict(ema=ec.view(-1), ema_coef=self._ema_coef)
             if pv is None or not g.is_contiguous():
                 # strided (channels_last) tensors: update through flat contiguous copies
                 pc = p.data.contiguous()
                 gc = g.contiguous()
                 bc = buf.contiguous() if buf is not None else None
                 C.sgd_step(pc.view(-1), gc.view(-1), bc.view(-1) if bc is not None else None, lr_t, lr, m, damp, wd,
-                           1.0, nest, first, maxim)
+                           1.0, nest, first, maxim, **ema)
                 p.data.copy_(pc)
                 if buf is not None and bc is not buf:
                     buf.copy_(bc)
             else:
                 C.sgd_step(pv.view(-1), g.view(-1), buf.view(-1) if buf is not None else None, lr_t, lr, m, damp,
-                           wd, 1.0, nest, first, maxim)
+                           wd, 1.0, nest, first, maxim, **ema)
+            if eb is not None and ec is not eb:
+                eb.copy_(ec)
             if m != 0.0:
                 st["momentum_buffer"] = buf
 
@@ -454,6 +614,9 @@ class SGD(Optimizer):
             clip = dict(clip_part=part, max_norm=self.max_grad_norm if self.max_grad_norm is not None else float("inf"),
                         stats=self._clip_stats, skip_nonfinite=self.skip_nonfinite)
         clip.update(self._flat_step_extra(C, arena, s, e, plan))
+        ema = arena.ema_buffer() if self._ema_decay is not None else None  # state[p]["ema_buffer"] are its views
+        if ema is not None:
+            clip.update(ema=ema[s:e], ema_coef=self._ema_coef)
         if plan is None:
             C.sgd_step(arena.data[s:e], arena.grad[s:e], mom, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, ctr,
                        **clip)
@@ -464,6 +627,8 @@ class SGD(Optimizer):
                 mk = mom[a - s:b - s] if mom is not None else None
                 c = ctr if k == last else None
                 ck = clip if k == last or not clip else dict(clip, stats=None)  # stats written once
+                if ema is not None:
+                    ck = dict(ck, ema=ema[a:b])
                 if sub is None:
                     C.sgd_step(arena.data[a:b], arena.grad[a:b], mk, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, c,
                                **ck)
@@ -497,6 +662,8 @@ class SGD(Optimizer):
                 buf.mul_(m).add_(d_p, alpha=1 - damp)
             d_p = d_p.add(buf, alpha=m) if group["nesterov"] else buf
         p.add_(d_p, alpha=-lr)
+        if self._ema_decay is not None:
+            self._ema_apply_reference(p)
 
 
 class LARS(SGD):
@@ -511,8 +678,8 @@ class LARS(SGD):
     and decayed when ``w.ndim > 1`` or ``exclude_bias_and_norm`` is false; with the default exclusion
     biases and BatchNorm weights get ``q = 1`` and no weight decay (the usual recipe), so the whole
     model stays one param group and one flat launch. Momentum, dampening, Nesterov, ``maximize``,
-    ``max_grad_norm`` / ``skip_nonfinite`` and the device-side learning rate (warm-up through
-    ``lr_tensor``) are :class:`SGD`'s. ``trust_coefficient``, ``eps`` and ``exclude_bias_and_norm``
+    ``max_grad_norm`` / ``skip_nonfinite``, ``ema_decay`` and the device-side learning rate (warm-up
+    through ``lr_tensor``) are :class:`SGD`'s. ``trust_coefficient``, ``eps`` and ``exclude_bias_and_norm``
     are ``param_groups`` entries. The defaults 0.001 and 1e-8 are the conventional ones of the paper
     and common implementations; nothing was measured to choose them.
 
@@ -542,6 +709,7 @@ class LARS(SGD):
         flat: bool = True,
         max_grad_norm: float | None = None,
         skip_nonfinite: bool = False,
+        ema_decay: float | None = None,
     ):
         if not float(trust_coefficient) >= 0.0:
             raise ValueError(f"Invalid trust_coefficient: {trust_coefficient}")
@@ -550,7 +718,7 @@ class LARS(SGD):
         self._extra_defaults = dict(trust_coefficient=float(trust_coefficient), eps=float(eps),
                                     exclude_bias_and_norm=bool(exclude_bias_and_norm))
         super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, maximize=maximize, flat=flat,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
         all_params = [p for g in self.param_groups for p in g["params"]]
         self._slot = {id(p): k for k, p in enumerate(all_params)}
         # allocated here, never inside a capture
@@ -650,6 +818,12 @@ class LARS(SGD):
                 self._trust[k].fill_(1.0)
                 d_p = g if not group["maximize"] else -g
             self._apply_reference(group, p, d_p)
+
+
+def _check_ema_decay(decay):
+    d = float(decay)
+    if math.isnan(d) or not 0.0 <= d <= 1.0:
+        raise ValueError(f"Invalid ema_decay: {decay}")
 
 
 @torch.no_grad()

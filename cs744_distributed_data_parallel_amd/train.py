@@ -194,10 +194,11 @@ def run(rank, size, epochs, batch_size, args):
     if args.optimizer == "lars":
         optimizer = LARS(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
                          trust_coefficient=args.trust_coefficient, max_grad_norm=args.clip_grad_norm,
-                         skip_nonfinite=args.skip_nonfinite)
+                         skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay)
     else:
         optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
-                        max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+                        max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite,
+                        ema_decay=args.ema_decay)
 
     start_epoch = 0
     if args.resume and args.checkpoint_dir:
@@ -221,6 +222,16 @@ def run(rank, size, epochs, batch_size, args):
             torch.cuda.synchronize()
         print("Training time after {} epoch is {}".format(epoch + 1, (time.time() - start_time)))
         test_model(model, test_loader, eval_criterion, topk=args.eval_topk)
+        if args.ema_decay is not None:
+            # once more with the averaged weights (stderr: stdout keeps the reference's lines); BatchNorm
+            # evaluates with the live running statistics
+            import sys
+
+            with optimizer.ema_weights():
+                ema_loss, ema_correct = test_model(model, test_loader, eval_criterion, print_fn=lambda *_: None)
+            total = len(test_loader.dataset)
+            print("[cdp] EMA weights: Average loss: {:.4f}, Accuracy: {}/{} ({:.0f}%)".format(
+                ema_loss, ema_correct, total, 100.0 * ema_correct / total), file=sys.stderr)
         if args.checkpoint_dir:
             save_checkpoint(os.path.join(args.checkpoint_dir, f"ckpt_{epoch + 1}.pt"), model, optimizer,
                             epoch=epoch + 1, rank=rank)
@@ -304,6 +315,9 @@ def parse_args(argv=None):
                    help="clip the global gradient 2-norm to this value inside the fused optimizer step")
     p.add_argument("--skip-nonfinite", action="store_true",
                    help="skip an optimizer step whose gradients hold an inf or a NaN")
+    p.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
+                   help="keep an exponential moving average of the weights inside the fused optimizer step and "
+                        "evaluate it too after every epoch (stderr); checkpoints carry it")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="FLOAT",
                    help="train against (1 - FLOAT) * onehot + FLOAT / classes (the test loss stays unsmoothed)")
     p.add_argument("--mixup-alpha", type=float, default=0.0, metavar="FLOAT",

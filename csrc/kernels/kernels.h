@@ -175,11 +175,19 @@ struct ClipArgs {
   float* stats = nullptr;
   int skip_nonfinite = 0;
 };
+// Weight EMA of a fused SGD step: e (laid out exactly like p; nullptr: off, the kernels run the
+// instantiations without it) gets e = fmaf(w_new, coef[1], e * coef[0]) per element, the arithmetic
+// of e.mul_(d).add_(w_new, alpha=1 - d). coef = {d, 1 - d} lives on the device so that a captured
+// step follows a decay schedule. A step skipped by the clip leaves e as it is.
+struct EmaArgs {
+  float* e = nullptr;
+  const float* coef = nullptr;
+};
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
                      bool maximize, hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{},
-                     const LarsArgs& lars = LarsArgs{});
+                     const LarsArgs& lars = LarsArgs{}, const EmaArgs& ema = EmaArgs{});
 void slab_sum_launch(const float* slab, int S, long long n, float* dst, bool accumulate, hipStream_t st);
 void slab_sum_strided_launch(const float* slab, int S, long long n_src, int src_cols, int dst_cols, float* dst,
                              bool accumulate, hipStream_t st);
@@ -285,7 +293,7 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
                 hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{},
-                const LarsArgs& lars = LarsArgs{});
+                const LarsArgs& lars = LarsArgs{}, const EmaArgs& ema = EmaArgs{});
 
 // grad_norm.hip: the global gradient norm of a flat fp32 range, in two deterministic stages.
 // grad_sumsq_launch writes P = grad_norm_parts(n) fp64 partial sums of squares, workgroup b over the

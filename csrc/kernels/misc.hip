@@ -342,6 +342,19 @@ __device__ __forceinline__ void sgd_upd(bool skip, float& p, float g, float& b, 
   }
   sgd_one(p, g, b, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
 }
+// Weight EMA (EMA instantiations only; EmaArgs in kernels.h): e = d * e + omd * w_new with the op
+// order of e.mul_(d).add_(w_new, alpha=omd). Every path of both kernels calls this one function, so
+// they all agree bitwise. A skipped step did not happen: e stays, and the store that follows writes
+// the same bits back.
+__device__ __forceinline__ float ema_one(float e, float w_new, float d, float omd) { return fmaf(w_new, omd, e * d); }
+template <bool CLIP>
+__device__ __forceinline__ void ema_upd(bool skip, float4& e, const float4& w, float d, float omd) {
+  if (CLIP && skip) return;
+  e.x = ema_one(e.x, w.x, d, omd);
+  e.y = ema_one(e.y, w.y, d, omd);
+  e.z = ema_one(e.z, w.z, d, omd);
+  e.w = ema_one(e.w, w.w, d, omd);
+}
 // gs *= coef and the skip decision, in the kernel's prologue (every workgroup gets the same bits);
 // workgroup 0 records norm / coef / skipped steps
 __device__ __forceinline__ bool sgd_clip_prologue(const ClipArgs& clip, float& gs) {
@@ -364,12 +377,13 @@ __device__ __forceinline__ void sgd_lars_prologue(const LarsArgs& lars, const La
   wd = (lars.exclude && !pr.matrix ? 0.f : wd) * q;
 }
 
-template <bool CLIP, bool LARS>
+template <bool CLIP, bool LARS, bool EMA>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                  long long n, const float* __restrict__ lr_ptr, float lr_host, float m,
                                                  float damp, float wd, float gs, int flags, long long* counter,
-                                                 ClipArgs clip, LarsArgs lars) {
+                                                 ClipArgs clip, LarsArgs lars, EmaArgs ema) {
   const bool nesterov = flags & 1, first = flags & 2, maximize = flags & 4, has_mom = flags & 8;
+  const float ed = EMA ? ema.coef[0] : 0.f, eomd = EMA ? ema.coef[1] : 0.f;
   // a data loader's step counter advanced by the step (one dispatch less per step; the counter is
   // read by this step's augment kernel, which ran before)
   if (counter && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1;
@@ -393,6 +407,11 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
       sgd_upd<CLIP>(skip, pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
       st4(p + e, pv);
       if (has_mom) st4(buf + e, bv);
+      if (EMA) {
+        float4 ev = ld4(ema.e + e);
+        ema_upd<CLIP>(skip, ev, pv, ed, eomd);
+        st4(ema.e + e, ev);
+      }
     }
     return;
   }
@@ -409,6 +428,11 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     sgd_upd<CLIP>(skip, pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
     st4(p + 4 * i, pv);
     if (has_mom) st4(buf + 4 * i, bv);
+    if (EMA) {
+      float4 ev = ld4(ema.e + 4 * i);
+      ema_upd<CLIP>(skip, ev, pv, ed, eomd);
+      st4(ema.e + 4 * i, ev);
+    }
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const long long i = (n4 << 2) + threadIdx.x;
@@ -417,6 +441,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     sgd_upd<CLIP>(skip, pp, g[i], has_mom ? bb : dummy, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
     p[i] = pp;
     if (has_mom) buf[i] = bb;
+    if (EMA && !(CLIP && skip)) ema.e[i] = ema_one(ema.e[i], pp, ed, eomd);
   }
 }
 
@@ -450,13 +475,17 @@ __device__ __forceinline__ void tile_max_store(const unsigned* s, float* __restr
 // sgd_one), store p / buf in place, then the |max| and the transpose of the NEW p through LDS.
 // Blocks [nblk_w, ...) each run sgd_kernel's float4 update over one chunk of the arena that no conv
 // weight covers (biases, BatchNorm parameters, the classifier).
-template <bool CLIP, bool LARS>
+// EMA: the weight average e (EmaArgs) is updated from the new p on every path. The tile paths load e
+// only after p and buf have left, into the registers of g and buf: measured with the compiler's
+// report, +2 to +3 VGPRs over the EMA = false instantiation, which is the kernel without this block.
+template <bool CLIP, bool LARS, bool EMA>
 __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ buf, const SgdPrepSeg* __restrict__ segs,
                                                       int nseg, int nblk_w, const SgdPrepChunk* __restrict__ chunks,
                                                       float* __restrict__ part, const float* __restrict__ lr_ptr,
                                                       float lr_host, float m, float damp, float wd, float gs,
-                                                      int flags, long long* counter, ClipArgs clip, LarsArgs lars) {
+                                                      int flags, long long* counter, ClipArgs clip, LarsArgs lars,
+                                                      EmaArgs ema) {
   // taps per group: 3 x 3 float4 in flight per thread keeps the kernel near 64 VGPRs (8 waves per
   // SIMD for this bandwidth-bound pass; a whole 3x3 filter per group held 256 VGPRs, 1 wave per SIMD)
   constexpr int TG = 3;
@@ -467,6 +496,7 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
   if (CLIP) skip = sgd_clip_prologue(clip, gs);  // as sgd_kernel; the |max| / W^T below are of the unchanged p
   const bool nesterov = flags & 1, first = flags & 2, maximize = flags & 4, has_mom = flags & 8;
   const float lr = lr_ptr ? lr_ptr[0] : lr_host;
+  const float ed = EMA ? ema.coef[0] : 0.f, eomd = EMA ? ema.coef[1] : 0.f;
   const int b = blockIdx.x;
   if (b >= nblk_w) {
     const SgdPrepChunk ch = chunks[b - nblk_w];
@@ -485,6 +515,11 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
       sgd_upd<CLIP>(skip, pv.w, gv.w, bv.w, lr, m, damp, wd, gs, nesterov, first, maximize, has_mom);
       st4(p + e, pv);
       if (has_mom) st4(buf + e, bv);
+      if (EMA) {
+        float4 ev = ld4(ema.e + e);
+        ema_upd<CLIP>(skip, ev, pv, ed, eomd);
+        st4(ema.e + e, ev);
+      }
     }
     return;
   }
@@ -503,6 +538,8 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
   const __amdgpu_buffer_rsrc_t pr = make_rsrc(pw, bytes);
   const __amdgpu_buffer_rsrc_t gr = make_rsrc(g + sg.off, bytes);
   const __amdgpu_buffer_rsrc_t br = make_rsrc(has_mom && !first ? bw : pw, bytes);
+  float* const ew = EMA ? ema.e + sg.off : pw;  // read only by the EMA instantiations
+  const __amdgpu_buffer_rsrc_t er = make_rsrc(ew, bytes);
   if (threadIdx.x < 64) smax[threadIdx.x] = 0u;
   __syncthreads();
   if ((Ci & 3) == 0) {
@@ -534,6 +571,17 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
           if (has_mom) st4(bw + (off[q] >> 2), vb[q]);
           mx4 = make_float4(fmaxf(mx4.x, fabsf(vp[q].x)), fmaxf(mx4.y, fabsf(vp[q].y)), fmaxf(mx4.z, fabsf(vp[q].z)),
                             fmaxf(mx4.w, fabsf(vp[q].w)));
+        }
+      }
+      if (EMA) {
+        // after p / buf left: e takes over the registers of g and buf, not a fourth array in flight
+        float4 ve[TG];
+#pragma unroll
+        for (int q = 0; q < TG; ++q) ve[q] = bload4(er, off[q]);
+#pragma unroll
+        for (int q = 0; q < TG; ++q) {
+          ema_upd<CLIP>(skip, ve[q], vp[q], ed, eomd);
+          if (off[q] != kOOB) st4(ew + (off[q] >> 2), ve[q]);
         }
       }
       if (wt) {
@@ -599,6 +647,19 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
             mco[jj] = fmaxf(mco[jj], fabsf(vp[q][jj]));
           }
         }
+      if (EMA) {
+        float ve[TG][4];
+#pragma unroll
+        for (int q = 0; q < TG; ++q)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj)
+            ve[q][jj] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(er, (int)off[q][jj], 0, 0));
+#pragma unroll
+        for (int q = 0; q < TG; ++q)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj)
+            if (off[q][jj] != kOOB && !(CLIP && skip)) ew[off[q][jj] >> 2] = ema_one(ve[q][jj], vp[q][jj], ed, eomd);
+      }
       if (wt) {
 #pragma unroll
         for (int q = 0; q < TG; ++q)
@@ -1341,34 +1402,47 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
 }
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
-                hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars) {
+                hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars, const EmaArgs& ema) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
-  if (lars.params) {  // one workgroup per item of the LARS work list, which tiles [0, n)
-    if (lars.nitems < 1) return;
-    if (clip.part)
-      hipLaunchKernelGGL((sgd_kernel<true, true>), dim3(lars.nitems), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
-                         momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
-    else
-      hipLaunchKernelGGL((sgd_kernel<false, true>), dim3(lars.nitems), dim3(256), 0, st, p, g, buf, n, lr_ptr, lr,
-                         momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
-    return;
+  if ((ema.e != nullptr) != (ema.coef != nullptr)) throw std::runtime_error("sgd: ema and ema_coef go together");
+  if (lars.params && lars.nitems < 1) return;
+  // LARS: one workgroup per item of the work list, which tiles [0, n)
+  const dim3 grid(lars.params ? lars.nitems : grid_for((n + 3) / 4));
+#define CDP_SGD(CLIP, LARS, EMA)                                                                                  \
+  hipLaunchKernelGGL((sgd_kernel<CLIP, LARS, EMA>), grid, dim3(256), 0, st, p, g, buf, n, lr_ptr, lr, momentum,  \
+                     dampening, wd, grad_scale, flags, counter, clip, lars, ema)
+#define CDP_SGD_E(CLIP, LARS)             \
+  do {                                    \
+    if (ema.e) CDP_SGD(CLIP, LARS, true); \
+    else CDP_SGD(CLIP, LARS, false);      \
+  } while (0)
+  if (lars.params) {
+    if (clip.part) CDP_SGD_E(true, true);
+    else CDP_SGD_E(false, true);
+  } else {
+    if (clip.part) CDP_SGD_E(true, false);
+    else CDP_SGD_E(false, false);
   }
-  if (clip.part)
-    hipLaunchKernelGGL((sgd_kernel<true, false>), dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr,
-                       lr, momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
-  else
-    hipLaunchKernelGGL((sgd_kernel<false, false>), dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, buf, n, lr_ptr,
-                       lr, momentum, dampening, wd, grad_scale, flags, counter, clip, lars);
+#undef CDP_SGD_E
+#undef CDP_SGD
 }
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
-                     bool maximize, hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars) {
+                     bool maximize, hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars,
+                     const EmaArgs& ema) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
+  if ((ema.e != nullptr) != (ema.coef != nullptr)) throw std::runtime_error("sgd: ema and ema_coef go together");
   if (nblk_w + nchunk <= 0) return;
-#define CDP_SGD_PREP(CLIP, LARS)                                                                                      \
-  hipLaunchKernelGGL((sgd_prep_kernel<CLIP, LARS>), dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, nseg,  \
-                     nblk_w, chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter, clip, lars)
+#define CDP_SGD_PREP_E(CLIP, LARS, EMA)                                                                             \
+  hipLaunchKernelGGL((sgd_prep_kernel<CLIP, LARS, EMA>), dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, \
+                     nseg, nblk_w, chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter,  \
+                     clip, lars, ema)
+#define CDP_SGD_PREP(CLIP, LARS)                 \
+  do {                                           \
+    if (ema.e) CDP_SGD_PREP_E(CLIP, LARS, true); \
+    else CDP_SGD_PREP_E(CLIP, LARS, false);      \
+  } while (0)
   if (lars.params) {
     if (clip.part) CDP_SGD_PREP(true, true);
     else CDP_SGD_PREP(false, true);
@@ -1377,6 +1451,7 @@ void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* seg
     else CDP_SGD_PREP(false, false);
   }
 #undef CDP_SGD_PREP
+#undef CDP_SGD_PREP_E
 }
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,

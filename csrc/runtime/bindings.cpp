@@ -120,7 +120,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("grad_scale"), py::arg("nesterov"),
         py::arg("first"), py::arg("maximize"), py::arg("counter") = py::none(), py::arg("clip_part") = py::none(),
         py::arg("max_norm") = 0.0, py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false,
-        py::arg("lars") = LarsStep{});
+        py::arg("lars") = LarsStep{}, py::arg("ema") = py::none(), py::arg("ema_coef") = py::none());
   m.def("grad_norm_parts", &grad_norm_parts_, py::arg("n"), "partials grad_sumsq writes for a range of n floats");
   m.def("grad_norm_chunk", &grad_norm_chunk_, py::arg("n"), "floats of the range each grad_sumsq workgroup owns");
   m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("part"),
@@ -136,6 +136,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("first"), py::arg("maximize"), py::arg("desc"), py::arg("meta"), py::arg("amax"),
         py::arg("counter") = py::none(), py::arg("clip_part") = py::none(), py::arg("max_norm") = 0.0,
         py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false, py::arg("lars") = LarsStep{},
+        py::arg("ema") = py::none(), py::arg("ema_coef") = py::none(),
         "SGD over an arena range that also emits the next step's weight |max| / W^T");
   m.def("augment", &augment, py::arg("images"), py::arg("indices"), py::arg("idx_offset"), py::arg("batch"),
         py::arg("mean"), py::arg("std"), py::arg("pad"), py::arg("flip"), py::arg("counter"), py::arg("seed"),

@@ -1976,6 +1976,23 @@ ClipArgs clip_args(const c10::optional<at::Tensor>& clip_part, double max_norm, 
   c.skip_nonfinite = skip_nonfinite ? 1 : 0;
   return c;
 }
+// the weight-EMA block of a fused SGD launch: ema is laid out exactly like p, ema_coef = {d, 1 - d}
+EmaArgs ema_args(const c10::optional<at::Tensor>& ema, const c10::optional<at::Tensor>& ema_coef, const at::Tensor& p) {
+  EmaArgs a;
+  const bool has_e = ema.has_value() && ema->defined(), has_c = ema_coef.has_value() && ema_coef->defined();
+  TORCH_CHECK(has_e == has_c, "sgd: ema and ema_coef go together");
+  if (!has_e) return a;
+  TORCH_CHECK(ema->is_cuda() && ema->device() == p.device() && ema->scalar_type() == at::kFloat &&
+                  ema->is_contiguous() && ema->numel() == p.numel() && aligned16(*ema) && aligned16(p),
+              "sgd: ema must be a contiguous 16-byte aligned float32 tensor of the parameters' size and device");
+  TORCH_CHECK(ema->data_ptr() != p.data_ptr(), "sgd: ema must not be the parameters' storage");
+  TORCH_CHECK(ema_coef->is_cuda() && ema_coef->device() == p.device() && ema_coef->scalar_type() == at::kFloat &&
+                  ema_coef->is_contiguous() && ema_coef->numel() >= 2,
+              "sgd: ema_coef must be a contiguous float32 device tensor {d, 1 - d}");
+  a.e = ema->data_ptr<float>();
+  a.coef = ema_coef->data_ptr<float>();
+  return a;
+}
 }  // namespace
 
 // ---------------------------------------------------------------- LARS
@@ -2164,9 +2181,11 @@ void clip_scale(at::Tensor g, const at::Tensor& part, double max_norm, const c10
 void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
               bool maximize, const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
-              double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite, const LarsStep& lars) {
+              double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite, const LarsStep& lars,
+              const c10::optional<at::Tensor>& ema, const c10::optional<at::Tensor>& ema_coef) {
   const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
+  const EmaArgs ea = ema_args(ema, ema_coef, p);
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
   float* bp = nullptr;
   if (momentum != 0.0) {
@@ -2180,7 +2199,7 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
   }
   sgd_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, p.numel(), fptr(lr_t), (float)lr, (float)momentum,
              (float)dampening, (float)wd, (float)grad_scale, nesterov, first, maximize, cur_stream(),
-             counter_ptr(counter), clip, la);
+             counter_ptr(counter), clip, la, ea);
 }
 
 // ---------------------------------------------------------------- SGD + next-step weight preparation
@@ -2278,9 +2297,11 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
                    bool maximize, const at::Tensor& desc, const at::Tensor& meta, at::Tensor amax,
                    const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
                    double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite,
-                   const LarsStep& lars) {
+                   const LarsStep& lars, const c10::optional<at::Tensor>& ema,
+                   const c10::optional<at::Tensor>& ema_coef) {
   const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
+  const EmaArgs ea = ema_args(ema, ema_coef, p);
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
   float* bp = nullptr;
   if (momentum != 0.0) {
@@ -2301,7 +2322,7 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
   sgd_prep_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, reinterpret_cast<const SgdPrepSeg*>(d), nseg, nblk,
                   reinterpret_cast<const SgdPrepChunk*>(d + nseg * sizeof(SgdPrepSeg)), nchunk,
                   amax.data_ptr<float>(), fptr(lr_t), (float)lr, (float)momentum, (float)dampening, (float)wd,
-                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter), clip, la);
+                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter), clip, la, ea);
 }
 
 // ---------------------------------------------------------------- data augmentation

@@ -114,13 +114,16 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
                    bool maximize, const at::Tensor& desc, const at::Tensor& meta, at::Tensor amax,
                    const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part = c10::nullopt,
                    double max_norm = 0.0, const c10::optional<at::Tensor>& stats = c10::nullopt,
-                   bool skip_nonfinite = false, const LarsStep& lars = LarsStep{});
+                   bool skip_nonfinite = false, const LarsStep& lars = LarsStep{},
+                   const c10::optional<at::Tensor>& ema = c10::nullopt,
+                   const c10::optional<at::Tensor>& ema_coef = c10::nullopt);
 void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
               bool maximize, const c10::optional<at::Tensor>& counter,
               const c10::optional<at::Tensor>& clip_part = c10::nullopt, double max_norm = 0.0,
               const c10::optional<at::Tensor>& stats = c10::nullopt, bool skip_nonfinite = false,
-              const LarsStep& lars = LarsStep{});
+              const LarsStep& lars = LarsStep{}, const c10::optional<at::Tensor>& ema = c10::nullopt,
+              const c10::optional<at::Tensor>& ema_coef = c10::nullopt);
 // gradient-norm clipping over a flat fp32 range (csrc/kernels/grad_norm.hip): part[0 .. grad_norm_parts(n))
 // fp64 partial sums of squares; clip_scale: g *= min(max_norm / (norm + 1e-6), 1), stats = {norm, coef, -}
 int64_t grad_norm_parts_(int64_t n);
