@@ -176,17 +176,53 @@ class DeviceLoader:
     paired with image ``B - 1 - b``. A batch is mixed with probability ``mix_prob``; with both alphas set
     it is CutMix with probability ``mix_switch_prob``, else mixup. The target is then a
     :class:`MixTarget`. With both alphas 0 the loader returns exactly what it returns without them.
+
+    ``rrc_scale=(lo, hi)`` (and ``train=True``) turns on RandomResizedCrop in the same kernel: per image a
+    window of ``U(lo, hi)`` of the stored area and an aspect ratio log-uniform in ``rrc_ratio``
+    (torchvision's ``get_params`` rule, drawn on the device from the step counter), resampled bilinearly
+    (``align_corners=False``, no antialias) to ``out_size`` (an int or ``(OH, OW)``; default: the stored
+    size), then the flip. It **replaces** the pad-shift RandomCrop: the dataset's ``pad`` is ignored. A
+    training loader has no other way to change the size, so ``out_size`` without ``rrc_scale`` is an error.
+    ``train=False`` with ``out_size`` and / or ``center_crop``: the central window of fraction
+    ``center_crop`` (default 1.0) of each side, resized to ``out_size``; no flip, no randomness
+    (``rrc_scale`` is ignored there, as the mix arguments are). The blend is not re-quantised to uint8
+    before the normalisation. Each batch's windows are kept in ``last_crops`` (int32 ``[B, 5]``:
+    ``top, left, h, w, flip``); mixup / CutMix compose (the CutMix box is in output pixels). With all four
+    arguments at their defaults the loader is exactly what it is without them, and ``last_crops`` is None.
     """
 
     def __init__(self, dataset: ImageDataset, batch_size: int, sampler=None, shuffle: bool = False,
                  train: bool = True, drop_last: bool = False, seed: int = 0, mixup_alpha: float = 0.0,
-                 cutmix_alpha: float = 0.0, mix_prob: float = 1.0, mix_switch_prob: float = 0.5):
+                 cutmix_alpha: float = 0.0, mix_prob: float = 1.0, mix_switch_prob: float = 0.5,
+                 out_size=None, rrc_scale=None, rrc_ratio=(3.0 / 4.0, 4.0 / 3.0), center_crop=None):
         if not (mixup_alpha >= 0.0 and cutmix_alpha >= 0.0):
             raise ValueError(f"mixup_alpha and cutmix_alpha must be >= 0. Got: {mixup_alpha}, {cutmix_alpha}")
         if not (0.0 <= mix_prob <= 1.0 and 0.0 <= mix_switch_prob <= 1.0):
             raise ValueError(f"mix_prob and mix_switch_prob must be in [0, 1]. Got: {mix_prob}, {mix_switch_prob}")
         self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
         self.mix_prob, self.mix_switch_prob = float(mix_prob), float(mix_switch_prob)
+        if rrc_scale is not None:
+            rrc_scale = tuple(float(v) for v in rrc_scale)
+            if not (len(rrc_scale) == 2 and 0.0 < rrc_scale[0] <= rrc_scale[1] <= 1.0):
+                raise ValueError(f"rrc_scale must be (lo, hi) with 0 < lo <= hi <= 1. Got: {rrc_scale}")
+        rrc_ratio = tuple(float(v) for v in rrc_ratio)
+        if not (len(rrc_ratio) == 2 and 0.0 < rrc_ratio[0] <= rrc_ratio[1] < math.inf):
+            raise ValueError(f"rrc_ratio must be (lo, hi) with 0 < lo <= hi. Got: {rrc_ratio}")
+        if center_crop is not None and not (0.0 < float(center_crop) <= 1.0):
+            raise ValueError(f"center_crop must be in (0, 1]. Got: {center_crop}")
+        if out_size is not None:
+            out_size = (out_size, out_size) if isinstance(out_size, int) else tuple(int(v) for v in out_size)
+            if not (len(out_size) == 2 and all(1 <= v < 32768 for v in out_size)):
+                raise ValueError(f"out_size must be an int or (OH, OW) with 1 <= OH, OW < 32768. Got: {out_size}")
+        if train and out_size is not None and rrc_scale is None:
+            raise ValueError(f"out_size={out_size} on a training loader needs rrc_scale: RandomResizedCrop is its "
+                             "only way to change the size")
+        self.rrc_scale, self.rrc_ratio = rrc_scale, rrc_ratio
+        self.center_crop = 1.0 if center_crop is None else float(center_crop)
+        # resizing: the augment_resize path (RandomResizedCrop when training, resize + center crop otherwise)
+        self.resizing = rrc_scale is not None if train else (out_size is not None or center_crop is not None)
+        self.out_size = out_size if out_size is not None else tuple(dataset.images.shape[1:3])
+        self.last_crops = None
         self.ds, self.batch_size, self.sampler, self.shuffle = dataset, batch_size, sampler, shuffle
         self.train, self.drop_last, self.seed = train, drop_last, seed
         self.dev = dataset.images.device
@@ -271,7 +307,26 @@ class DeviceLoader:
         if self.dev.type == "cuda":
             C = _native.lib()
             target = torch.empty(bsz, dtype=torch.int64, device=self.dev)
-            if self.mixing:
+            if self.resizing:
+                OH, OW = self.out_size
+                if out is not None and tuple(out.shape) != (bsz, self.ds.shape[2], OH, OW):
+                    raise ValueError(f"DeviceLoader.batch: out has shape {tuple(out.shape)}, the batch is "
+                                     f"{(bsz, self.ds.shape[2], OH, OW)}")
+                crops = torch.empty(bsz, 5, dtype=torch.int32, device=self.dev)
+                args = (self.ds.images, idx, offset, bsz, self.ds.mean, self.ds.std, OH, OW, self.train,
+                        self.rrc_scale or (1.0, 1.0), self.rrc_ratio, self.center_crop, flip, self._counter,
+                        self.seed, out, nbatches, self.ds.labels, target, crops)
+                if self.mixing:
+                    target_b = torch.empty(bsz, dtype=torch.int64, device=self.dev)
+                    info = torch.empty(8, dtype=torch.float32, device=self.dev)
+                    data = C.augment_resize(*args, mixup_alpha=self.mixup_alpha, cutmix_alpha=self.cutmix_alpha,
+                                            mix_prob=self.mix_prob, mix_switch_prob=self.mix_switch_prob, mix=info,
+                                            labels_b=target_b)
+                    target = MixTarget(target, target_b, info[1:2], info)
+                else:
+                    data = C.augment_resize(*args)
+                self.last_crops = crops
+            elif self.mixing:
                 # the same launch draws the batch's mix from the step counter, applies it and publishes it
                 target_b = torch.empty(bsz, dtype=torch.int64, device=self.dev)
                 info = torch.empty(8, dtype=torch.float32, device=self.dev)
@@ -288,9 +343,15 @@ class DeviceLoader:
             else:
                 self._check_one_batch_per_step()
             return data, target
-        ctr = int(self._counter.item()) if (nbatches > 0 or self.mixing) else None
+        ctr = int(self._counter.item()) if (nbatches > 0 or self.mixing or self.resizing) else None
         if nbatches > 0:
             offset += (ctr % nbatches) * bsz
+        if self.resizing:
+            self._counter += 1
+            data, target = self._cpu_resize_batch(idx[offset : offset + bsz], flip, ctr)
+            if out is not None:
+                data = out.copy_(data)
+            return self._cpu_mix(data, target, ctr) if self.mixing else (data, target)
         if ctr is not None and not pad:
             self._counter += 1  # (the padded path advances it itself)
         data, target = self._cpu_batch(idx[offset : offset + bsz], pad, flip)
@@ -301,9 +362,68 @@ class DeviceLoader:
     def mix_schedule(self, first_counter: int, n: int) -> torch.Tensor:
         """The rows ``{mode, lam, lam_raw, y0, y1, x0, x1, 0}`` that the batches at step counters
         ``first_counter .. first_counter + n - 1`` publish (float32 ``[n, 8]``; GPU loaders)."""
-        H, W = self.ds.shape[:2]
+        H, W = self.out_size if self.resizing else self.ds.shape[:2]
         return _native.lib().mix_params(self.seed, first_counter, n, self.mixup_alpha, self.cutmix_alpha,
                                         self.mix_prob, self.mix_switch_prob, H, W)
+
+    def crop_schedule(self, first_counter: int, n: int, B: int) -> torch.Tensor:
+        """The RandomResizedCrop windows ``{top, left, h, w}`` of the ``B`` images of the batches at step
+        counters ``first_counter .. first_counter + n - 1`` (int32 ``[n, B, 4]``; GPU training loaders with
+        ``rrc_scale``)."""
+        if not (self.train and self.rrc_scale is not None):
+            raise ValueError("crop_schedule: a training loader with rrc_scale draws windows; this one does not")
+        H, W = self.ds.shape[:2]
+        return _native.lib().rrc_params(self.seed, first_counter, n, B, self.rrc_scale, self.rrc_ratio, H, W)
+
+    @staticmethod
+    def _rrc_get_params(H, W, scale, ratio, g):
+        """torchvision's ``RandomResizedCrop.get_params`` rule with draws from the generator ``g``."""
+        area = H * W
+        log_lo, log_hi = math.log(ratio[0]), math.log(ratio[1])
+        for _ in range(10):
+            u_s, u_r, u_t, u_l = torch.rand(4, generator=g, dtype=torch.float64).tolist()
+            target = area * (scale[0] + (scale[1] - scale[0]) * u_s)
+            aspect = math.exp(log_lo + (log_hi - log_lo) * u_r)
+            w, h = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+            if 0 < w <= W and 0 < h <= H:
+                return min(int(u_t * (H - h + 1)), H - h), min(int(u_l * (W - w + 1)), W - w), h, w
+        in_ratio = W / H
+        h, w = H, W
+        if in_ratio < ratio[0]:
+            h = min(max(int(round(W / ratio[0])), 1), H)
+        elif in_ratio > ratio[1]:
+            w = min(max(int(round(H * ratio[1])), 1), W)
+        return (H - h) // 2, (W - w) // 2, h, w
+
+    def _cpu_resize_batch(self, sel, flip, ctr):
+        """The resize kernel's semantics on the host: per image the window rule (a generator of its own,
+        seeded apart from the crop / flip and the mix generators), ``F.interpolate`` of the window
+        (bilinear, ``align_corners=False``, no antialias, not re-quantised), the flip, the normalisation."""
+        H, W = self.ds.shape[:2]
+        OH, OW = self.out_size
+        g = torch.Generator().manual_seed((0x727263 << 40) + self.seed * 1000003 + ctr)
+        # fp64: F.interpolate in fp32 rounds the source coordinate itself, the kernel's integer form does not
+        imgs = self.ds.images.index_select(0, sel).permute(0, 3, 1, 2).double()  # NCHW, 0 .. 255
+        B = imgs.shape[0]
+        out = torch.empty(B, imgs.shape[1], OH, OW, dtype=torch.float64)
+        crops = torch.zeros(B, 5, dtype=torch.int32)
+        eh, ew = max(1, int(round(self.center_crop * H))), max(1, int(round(self.center_crop * W)))
+        for b in range(B):
+            if self.train:
+                top, left, h, w = self._rrc_get_params(H, W, self.rrc_scale, self.rrc_ratio, g)
+                fl = bool(flip) and float(torch.rand(1, generator=g)) < 0.5
+            else:
+                top, left, h, w, fl = (H - eh) // 2, (W - ew) // 2, eh, ew, False
+            win = imgs[b : b + 1, :, top : top + h, left : left + w]
+            res = torch.nn.functional.interpolate(win, size=(OH, OW), mode="bilinear", align_corners=False,
+                                                  antialias=False)[0]
+            out[b] = res.flip(-1) if fl else res
+            crops[b] = torch.tensor([top, left, h, w, int(fl)], dtype=torch.int32)
+        self.last_crops = crops
+        mean = torch.tensor(self.ds.mean, dtype=torch.float64).view(1, -1, 1, 1)
+        std = torch.tensor(self.ds.std, dtype=torch.float64).view(1, -1, 1, 1)
+        out = ((out / 255.0 - mean) / std).float()
+        return out.contiguous(memory_format=torch.channels_last), self.ds.labels.index_select(0, sel)
 
     def _cpu_mix(self, data, target, ctr):
         """The device kernel's semantics on the host: one draw per batch from a generator of its own

@@ -111,6 +111,14 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 info = target.info.tolist()
                 print("[cdp] rank {}: mix in iter {} is mode {} lam {}".format(
                     rank, iter_number, MIX_MODES[int(info[0])], info[1]), file=sys.stderr)
+            crops = getattr(train_loader, "last_crops", None)
+            if crops is not None and not (data.is_cuda and torch.cuda.is_current_stream_capturing()):
+                # RandomResizedCrop: the first image's window in the window's last batch (stderr, as above)
+                import sys
+
+                top, left, h, w = crops[0, :4].tolist()
+                print("[cdp] rank {}: crop of image 0 in iter {} is {} x {} at ({}, {})".format(
+                    rank, iter_number, h, w, top, left), file=sys.stderr)
         if max_iters is not None and iter_number >= max_iters:
             break
         iter_number += 1
@@ -154,7 +162,7 @@ def build_data(args, device, train: bool):
         return cifar10_binary(args.data.split(":", 1)[1], train=train, device=device)
     if args.model.startswith("resnet"):
         n = args.synthetic_size or (1281 if train else 500)
-        return synthetic_imagenet(n, seed=0 if train else 1, device=device)
+        return synthetic_imagenet(n, seed=0 if train else 1, device=device, size=args.stored_size)
     n = args.synthetic_size or (50000 if train else 10000)
     return synthetic_cifar10(n, seed=0, device=device, train=train, learnable=args.data == "synthetic-learnable")
 
@@ -168,10 +176,13 @@ def run(rank, size, epochs, batch_size, args):
     # mixup / CutMix shape the training batches only: the test loader below takes none of it
     train_loader = DeviceLoader(training_set, batch_size, sampler=train_sampler, shuffle=(size == 1), train=True,
                                 seed=args.seed, mixup_alpha=args.mixup_alpha, cutmix_alpha=args.cutmix_alpha,
-                                mix_prob=args.mix_prob, mix_switch_prob=args.mix_switch_prob)
+                                mix_prob=args.mix_prob, mix_switch_prob=args.mix_switch_prob,
+                                out_size=args.crop_size if args.rrc_scale is not None else None,
+                                rrc_scale=args.rrc_scale, rrc_ratio=args.rrc_ratio)
     print("Size of training set is {}".format(len(train_loader)))
     test_set = build_data(args, device, False)
-    test_loader = DeviceLoader(test_set, batch_size, shuffle=False, train=False)
+    test_loader = DeviceLoader(test_set, batch_size, shuffle=False, train=False, out_size=args.crop_size,
+                               center_crop=args.center_crop)
     print("Size of test set is {}".format(len(test_loader)))
 
     if dist.is_initialized() and device.type == "cuda":
@@ -328,6 +339,17 @@ def parse_args(argv=None):
                    help="probability that a training batch is mixed at all (with --mixup-alpha / --cutmix-alpha)")
     p.add_argument("--mix-switch-prob", type=float, default=0.5, metavar="FLOAT",
                    help="probability of CutMix over mixup when both alphas are set")
+    p.add_argument("--rrc-scale", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="RandomResizedCrop on the training loader: a window of U(LO, HI) of the image area, resized "
+                        "to --crop-size (replaces the pad-shift RandomCrop)")
+    p.add_argument("--rrc-ratio", type=float, nargs=2, default=(3.0 / 4.0, 4.0 / 3.0), metavar=("LO", "HI"),
+                   help="aspect ratio range of the RandomResizedCrop window (log-uniform)")
+    p.add_argument("--crop-size", type=int, default=None, metavar="S",
+                   help="output side of both loaders (training: with --rrc-scale; default: the stored size)")
+    p.add_argument("--center-crop", type=float, default=None, metavar="FRAC",
+                   help="test loader: the central FRAC of each side, resized to --crop-size")
+    p.add_argument("--stored-size", type=int, default=224, metavar="S",
+                   help="side of the synthetic ImageNet-shaped images (resnet models)")
     p.add_argument("--eval-topk", type=int, default=None, metavar="K",
                    help="also report the top-K accuracy of the test set (stderr; ties go to the lower class index)")
     p.add_argument("--bucket-cap-mb", type=float, default=None)

@@ -6,6 +6,7 @@
 
 #include "lars.h"
 #include "mix.h"
+#include "rrc.h"
 
 namespace cdp {
 
@@ -329,6 +330,20 @@ void augment_launch(const unsigned char* imgs, const long long* idx, long long i
 // mix[i][kMixRow] = the row the augment kernel publishes at step counter first + i, i < n
 void mix_params_launch(unsigned long long seed, long long first, long long n, const MixCfg& cfg, int H, int W,
                        float* mix, hipStream_t st);
+// The augment launch with a resize (3-channel images): out[b] (NHWC fp32, OH x OW) is a window of image b
+// resampled bilinearly. train: the window is rrc_draw(seed, counter, b, rc, H, W) (rrc.h); otherwise the central
+// (round(center_frac H), round(center_frac W)). crops[b][kCropRow] = {top, left, h, w, flip}. idx, nbatches,
+// labels and the mix arguments are augment_launch's; the CutMix box is in output pixels.
+void augment_resize_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W,
+                           int C, int OH, int OW, const float* mean, const float* inv_std, bool train,
+                           const RrcCfg& rc, double center_frac, bool flip, const long long* counter,
+                           unsigned long long seed, float* out, hipStream_t st, long long nbatches,
+                           const long long* labels, long long* labels_out, int* crops,
+                           const MixCfg& cfg = MixCfg{0.f, 0.f, 1.f, 0.5f}, float* mix = nullptr,
+                           long long* labels_b = nullptr);
+// win[i][b][4] = the window {top, left, h, w} of step counter first + i and image slot b, i < n, b < B
+void rrc_params_launch(unsigned long long seed, long long first, long long n, int B, const RrcCfg& rc, int H, int W,
+                       int* win, hipStream_t st);
 // zeros into the NHWC dX pixels of the sub-pixel parity classes set in mask (bit 2 ph + pw)
 // dst[0 .. bytes) = src[0 .. bytes) as a kernel (16-B accesses when both pointers and bytes allow)
 void copy_bytes_launch(void* dst, const void* src, long long bytes, hipStream_t st);

@@ -9,6 +9,8 @@
 //   RandomCrop(32,4)+HFlip+Normalize    /root/reference/src/Part 1/main.py:82-93
 //   torch.mean(torch.stack(inputs), 0)  /root/reference/src/Part 2a/main.py:122
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include <stdexcept>
 
 #include "act_max.h"
@@ -17,6 +19,7 @@
 #include "lars.h"
 #include "kernels.h"
 #include "mix.h"
+#include "rrc.h"
 #include "x3_common.h"
 
 namespace cdp {
@@ -824,6 +827,203 @@ __global__ __launch_bounds__(256) void mix_params_kernel(unsigned long long seed
   mix_publish(mix + i * kMixRow, mix_draw(seed, (unsigned long long)(first + i), cfg, H, W));
 }
 
+// ------------------------------------------------------------------ augmentation with a resize
+// out[b][y][x][c] (NHWC fp32, OH x OW) from a window {top, left, h, w} of the uint8 HWC images[idx[b]]:
+// RandomResizedCrop (train: the window is rrc_draw's, rrc.h) or resize + center crop (eval: the central
+// window the launcher computed), then the flip of aug_image's hash, ToTensor and Normalize. Bilinear,
+// align_corners = false, no antialias, evaluated inside the window (neighbours clamp at the window's
+// edge: torchvision's crop-then-resize). The source coordinate of output index o of an axis of
+// n_out from n_in is exact in integers: with n = max((2 o + 1) n_in - n_out, 0),
+//   i0 = n / (2 n_out), i1 = min(i0 + 1, n_in - 1), lam = float(n % (2 n_out)) / float(2 n_out)
+// so each weight carries one rounding. The blend is in the 0 .. 255 domain and is not re-quantised to
+// uint8 before the normalisation. Every sum of two products is written as one product and one fmaf:
+// the build contracts (-ffp-contract=fast fuses a product into a sum wherever it finds one, differently
+// from one caller to the next, and no pragma stops it), and the MIX instantiation must give the bits of
+// the plain one; in this form nothing is left to fuse.
+struct RszWin {  // an image's window and flip, as the drawing lane leaves them in LDS
+  int top, left, h, w, fl;
+};
+struct RszTap {  // the two neighbours along one axis and the weight of the second
+  int i0, i1;
+  float lam;
+  int pad_;
+};
+constexpr int kRszCols = 1024;  // output columns per pass: 4 per thread
+
+__device__ __forceinline__ RszTap rsz_tap(int o, int n_in, int n_out) {
+  const unsigned num = (unsigned)max((2 * o + 1) * n_in - n_out, 0);  // < 2^31 for sizes < 32768
+  const unsigned den = 2u * (unsigned)n_out;
+  const unsigned i0 = num / den;
+  RszTap t;
+  t.i0 = min((int)i0, n_in - 1);
+  t.i1 = min((int)i0 + 1, n_in - 1);
+  t.lam = (float)(num - i0 * den) / (float)den;
+  t.pad_ = 0;
+  return t;
+}
+__device__ __forceinline__ RszWin rsz_window(int train, const RrcCfg& rc, int eh, int ew, int flip,
+                                             unsigned long long seed, unsigned long long ctr, int b, int H, int W) {
+  RrcWindow r{(H - eh) / 2, (W - ew) / 2, eh, ew};
+  if (train) r = rrc_draw(seed, ctr, b, rc, H, W);
+  // the flip bit of aug_image's hash: the same bit with the resize on or off
+  const AugImage a = aug_image(nullptr, 0, H, W, 3, 0, flip, seed, ctr, b);
+  return RszWin{r.top, r.left, r.h, r.w, a.fl ? 1 : 0};
+}
+// the rows of an image's window that output row y blends, and their weights
+struct RszRows {
+  const unsigned char* r0;
+  const unsigned char* r1;
+  float w0, w1;
+};
+__device__ __forceinline__ RszRows rsz_rows(const unsigned char* __restrict__ imgs, long long src_i, const RszWin& wn,
+                                            int y, int H, int W, int OH) {
+  const RszTap t = rsz_tap(y, wn.h, OH);
+  const unsigned char* base = imgs + (src_i * H + wn.top) * (long long)W * 3 + (long long)wn.left * 3;
+  return RszRows{base + (long long)t.i0 * W * 3, base + (long long)t.i1 * W * 3, 1.f - t.lam, t.lam};
+}
+// channel c of one output pixel, normalised ((v / 255 - mean) / std, the plain kernel's expression)
+__device__ __forceinline__ float rsz_sample(const RszRows& rw, const RszTap& ct, int c, float mean, float istd) {
+  const int o0 = ct.i0 * 3 + c, o1 = ct.i1 * 3 + c;
+  const float wx0 = 1.f - ct.lam, wx1 = ct.lam;
+  const float t = fmaf(wx1, (float)rw.r0[o1], wx0 * (float)rw.r0[o0]);
+  const float u = fmaf(wx1, (float)rw.r1[o1], wx0 * (float)rw.r1[o0]);
+  const float v = fmaf(rw.w1, u, rw.w0 * t);
+  return fmaf(v, 1.f / 255.f, -mean) * istd;
+}
+
+// Shape of the work: blockIdx.y = image, blockIdx.x strides over passes of 256 / (quads per row) rows.
+// A thread owns 4 consecutive output pixels of a row (12 contiguous floats: three 16-byte stores when
+// OW % 4 == 0 and out is 16-byte aligned, `vec`; scalar stores otherwise) and keeps its columns over
+// its rows. Thread 0 evaluates the window (under MIX also the partner's and the batch's mix) and shares
+// it through LDS; the per-column taps (flip included) are computed once per workgroup, also in LDS.
+// MIX: as augment_kernel's, with X the batch the <false> instantiation writes: the partner p = B - 1 - b
+// is resampled through its own window and flip, and the CutMix box is in output pixels.
+template <bool MIX>
+__global__ __launch_bounds__(256) void augment_resize_kernel(
+    const unsigned char* __restrict__ imgs, const long long* __restrict__ idx, long long idx_off, int B, int H, int W,
+    int OH, int OW, float m0, float m1, float m2, float is0, float is1, float is2, int train, RrcCfg rc, int eh, int ew,
+    int flip, const long long* __restrict__ counter, unsigned long long seed, float* __restrict__ out,
+    long long nbatches, const long long* __restrict__ labels, long long* __restrict__ labels_out,
+    int* __restrict__ crops, MixCfg cfg, float* __restrict__ mix, long long* __restrict__ labels_b, int vec) {
+  constexpr int NI = MIX ? 2 : 1;
+  __shared__ RszWin s_win[NI];
+  __shared__ MixParams s_mp;
+  __shared__ RszTap s_tap[NI][kRszCols];
+  const int b = blockIdx.y;
+  if (b >= B) return;
+  const unsigned long long ctr = counter ? (unsigned long long)counter[0] : 0ull;
+  const long long off = nbatches > 0 ? idx_off + (long long)(ctr % (unsigned long long)nbatches) * B : idx_off;
+  const int p = B - 1 - b;
+  const long long src_a = idx ? idx[off + b] : (off + b);
+  const long long src_p = MIX ? (idx ? idx[off + p] : (off + p)) : src_a;
+  if (threadIdx.x == 0) {
+    const RszWin wa = rsz_window(train, rc, eh, ew, flip, seed, ctr, b, H, W);
+    s_win[0] = wa;
+    MixParams mp{kMixNone, 1.f, 1.f, 0, 0, 0, 0};
+    if (MIX) {
+      mp = mix_draw(seed, ctr, cfg, OH, OW);
+      s_win[NI - 1] = rsz_window(train, rc, eh, ew, flip, seed, ctr, p, H, W);
+    }
+    s_mp = mp;
+    if (blockIdx.x == 0) {
+      if (labels_out) labels_out[b] = labels[src_a];
+      int* row = crops + (long long)b * kCropRow;
+      row[0] = wa.top;
+      row[1] = wa.left;
+      row[2] = wa.h;
+      row[3] = wa.w;
+      row[4] = wa.fl;
+      if (MIX) {
+        if (labels_b) labels_b[b] = labels[src_p];
+        if (b == 0 && mix) mix_publish(mix, mp);
+      }
+    }
+  }
+  __syncthreads();
+  const RszWin wa = s_win[0], wp = s_win[NI - 1];
+  const int mode = MIX ? s_mp.mode : kMixNone;  // uniform over the grid
+  const int by0 = s_mp.y0, by1 = s_mp.y1, bx0 = s_mp.x0, bx1 = s_mp.x1;
+  const float lam = s_mp.lam, oml = 1.f - s_mp.lam;
+  const float mean[3] = {m0, m1, m2};
+  const float istd[3] = {is0, is1, is2};
+  const int nq = (OW + 3) >> 2;           // quads per row
+  const int nqt = nq < 256 ? nq : 256;    // quads per pass
+  const int rpp = 256 / nqt;              // rows per pass
+  const int r = threadIdx.x / nqt, q = threadIdx.x - r * nqt;
+  float* dst = out + (long long)b * OH * OW * 3;
+  for (int c0 = 0; c0 < OW; c0 += kRszCols) {
+    if (c0) __syncthreads();  // the previous pass's readers are done with the taps
+    const int ncol = min(kRszCols, OW - c0);
+    for (int x = threadIdx.x; x < ncol; x += 256) {
+      const int xo = c0 + x;
+      s_tap[0][x] = rsz_tap(wa.fl ? OW - 1 - xo : xo, wa.w, OW);  // flip after the resize (torchvision order)
+      if (MIX && mode != kMixNone) s_tap[NI - 1][x] = rsz_tap(wp.fl ? OW - 1 - xo : xo, wp.w, OW);
+    }
+    __syncthreads();
+    const int x0 = c0 + 4 * q;
+    if (r >= rpp || x0 >= OW) continue;
+    for (int y = blockIdx.x * rpp + r; y < OH; y += gridDim.x * rpp) {
+      const RszRows ra = rsz_rows(imgs, src_a, wa, y, H, W, OH);
+      RszRows rb = ra;
+      if (MIX && mode != kMixNone) rb = rsz_rows(imgs, src_p, wp, y, H, W, OH);
+      float v[12];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int x = x0 + j;
+        const int xl = min(x, OW - 1) - c0;  // (a lane past the row's end computes its last pixel again)
+        const RszTap ta = s_tap[0][xl];
+        if (MIX && mode == kMixMixup) {
+          const RszTap tb = s_tap[NI - 1][xl];
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            v[3 * j + c] = lam * rsz_sample(ra, ta, c, mean[c], istd[c]) + oml * rsz_sample(rb, tb, c, mean[c], istd[c]);
+        } else if (MIX && mode == kMixCutmix) {
+          // the pixel comes whole from the partner inside the box, from the image itself outside
+          const bool box = y >= by0 && y < by1 && x >= bx0 && x < bx1;
+          const RszTap ts = box ? s_tap[NI - 1][xl] : ta;
+          RszRows rs;
+          rs.r0 = box ? rb.r0 : ra.r0;
+          rs.r1 = box ? rb.r1 : ra.r1;
+          rs.w0 = box ? rb.w0 : ra.w0;
+          rs.w1 = box ? rb.w1 : ra.w1;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) v[3 * j + c] = rsz_sample(rs, ts, c, mean[c], istd[c]);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) v[3 * j + c] = rsz_sample(ra, ta, c, mean[c], istd[c]);
+        }
+      }
+      float* o = dst + ((long long)y * OW + x0) * 3;
+      if (vec) {  // OW % 4 == 0: the quad is whole and 16-byte aligned
+        st4(o, make_float4(v[0], v[1], v[2], v[3]));
+        st4(o + 4, make_float4(v[4], v[5], v[6], v[7]));
+        st4(o + 8, make_float4(v[8], v[9], v[10], v[11]));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (x0 + j < OW) {
+            o[3 * j] = v[3 * j];
+            o[3 * j + 1] = v[3 * j + 1];
+            o[3 * j + 2] = v[3 * j + 2];
+          }
+      }
+    }
+  }
+}
+
+// win[i][b] = {top, left, h, w}: rrc_draw of step counter first + i and image slot b, i < n (the windows a
+// loader will publish, for logging and for the distribution tests)
+__global__ __launch_bounds__(256) void rrc_params_kernel(unsigned long long seed, long long first, long long total,
+                                                        int B, RrcCfg rc, int H, int W, int* __restrict__ win) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const RrcWindow r = rrc_draw(seed, (unsigned long long)(first + i / B), (int)(i % B), rc, H, W);
+  win[4 * i] = r.top;
+  win[4 * i + 1] = r.left;
+  win[4 * i + 2] = r.h;
+  win[4 * i + 3] = r.w;
+}
+
 __global__ void counter_inc_kernel(long long* c) { c[0] += 1; }
 
 // dX of a stride-2 conv's sub-pixel parity classes with no filter taps (bit 2 ph + pw of mask):
@@ -1479,6 +1679,54 @@ void mix_params_launch(unsigned long long seed, long long first, long long n, co
     throw std::runtime_error("mix_params: mix alphas >= 0, probabilities in [0, 1], H, W >= 1");
   hipLaunchKernelGGL(mix_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, seed, first, n, cfg, H, W,
                      mix);
+}
+namespace {
+bool rrc_cfg_ok(const RrcCfg& rc) {
+  return rc.scale_lo > 0.f && rc.scale_lo <= rc.scale_hi && rc.scale_hi <= 1.f && rc.log_ratio_lo <= rc.log_ratio_hi;
+}
+}  // namespace
+void augment_resize_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W,
+                           int C, int OH, int OW, const float* mean, const float* inv_std, bool train,
+                           const RrcCfg& rc, double center_frac, bool flip, const long long* counter,
+                           unsigned long long seed, float* out, hipStream_t st, long long nbatches,
+                           const long long* labels, long long* labels_out, int* crops, const MixCfg& cfg, float* mix,
+                           long long* labels_b) {
+  if (C != 3) throw std::runtime_error("augment_resize: 3-channel images only");
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || OH < 1 || OW < 1 || H > 0x7fff || W > 0x7fff || OH > 0x7fff || OW > 0x7fff)
+    throw std::runtime_error("augment_resize: 1 <= batch < 65536 and 1 <= H, W, out_h, out_w < 32768");
+  if (!crops || (labels_out && !labels)) throw std::runtime_error("augment_resize: crops (and labels for labels_out) needed");
+  if (!rrc_cfg_ok(rc) || !(center_frac > 0.0 && center_frac <= 1.0))
+    throw std::runtime_error("augment_resize: 0 < scale_lo <= scale_hi <= 1, ratio_lo <= ratio_hi, 0 < center_frac <= 1");
+  const bool mixing = mix_enabled(cfg);
+  if (mixing && (!mix || (labels_b && !labels)))
+    throw std::runtime_error("augment_resize: mixing needs the mix row (and labels for labels_b)");
+  if (!(cfg.mixup_alpha >= 0.f && cfg.cutmix_alpha >= 0.f && cfg.prob >= 0.f && cfg.prob <= 1.f &&
+        cfg.switch_prob >= 0.f && cfg.switch_prob <= 1.f))
+    throw std::runtime_error("augment_resize: mix alphas >= 0 and probabilities in [0, 1]");
+  // the eval window: the central (round(frac H), round(frac W)), ties to even as Python's round()
+  const int eh = std::max(1, std::min(H, (int)std::nearbyint(center_frac * H)));
+  const int ew = std::max(1, std::min(W, (int)std::nearbyint(center_frac * W)));
+  // few, large workgroups per image: every thread keeps its 4 columns over about 4 rows, and small
+  // batches still fill the chip
+  const int nq = (OW + 3) / 4;
+  const int rpp = 256 / std::min(nq, 256);
+  const int passes = (OH + rpp - 1) / rpp;
+  int gx = (passes + 3) / 4;
+  if ((long long)gx * B < 512) gx = std::min(passes, (512 + B - 1) / B);
+  const int vec = (OW % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
+  auto kern = mixing ? augment_resize_kernel<true> : augment_resize_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(gx, B), dim3(256), 0, st, imgs, idx, idx_off, B, H, W, OH, OW, mean[0], mean[1],
+                     mean[2], inv_std[0], inv_std[1], inv_std[2], train ? 1 : 0, rc, eh, ew, flip ? 1 : 0, counter,
+                     seed, out, nbatches, labels, labels_out, crops, cfg, mix, labels_b, vec);
+}
+void rrc_params_launch(unsigned long long seed, long long first, long long n, int B, const RrcCfg& rc, int H, int W,
+                       int* win, hipStream_t st) {
+  if (n <= 0 || B <= 0) return;
+  if (!rrc_cfg_ok(rc) || H < 1 || W < 1 || H > 0x7fff || W > 0x7fff)
+    throw std::runtime_error("rrc_params: 0 < scale_lo <= scale_hi <= 1, ratio_lo <= ratio_hi, 1 <= H, W < 32768");
+  const long long total = n * B;
+  hipLaunchKernelGGL(rrc_params_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, seed, first, total, B,
+                     rc, H, W, win);
 }
 void subpixel_zero_launch(float* dx, int N, int H, int W, int C, int mask, hipStream_t st) {
   if ((long long)N * H * W >= (1LL << 31) || (C & 3)) throw std::runtime_error("subpixel_zero: bad shape");

@@ -152,6 +152,20 @@ PYBIND11_MODULE(_C, m) {
         py::arg("mixup_alpha") = 0.0, py::arg("cutmix_alpha") = 0.0, py::arg("mix_prob") = 1.0,
         py::arg("mix_switch_prob") = 0.5, py::arg("H") = 32, py::arg("W") = 32,
         "float32 [n, 8]: the mix rows augment publishes at step counters first_counter .. first_counter + n - 1");
+  m.def("augment_resize", &augment_resize, py::arg("images"), py::arg("indices"), py::arg("idx_offset"),
+        py::arg("batch"), py::arg("mean"), py::arg("std"), py::arg("out_h"), py::arg("out_w"), py::arg("train"),
+        py::arg("scale"), py::arg("ratio"), py::arg("center_frac"), py::arg("flip"), py::arg("counter"),
+        py::arg("seed"), py::arg("out") = py::none(), py::arg("nbatches") = 0, py::arg("labels") = py::none(),
+        py::arg("labels_out") = py::none(), py::arg("crops"), py::arg("mixup_alpha") = 0.0,
+        py::arg("cutmix_alpha") = 0.0, py::arg("mix_prob") = 1.0, py::arg("mix_switch_prob") = 0.5,
+        py::arg("mix") = py::none(), py::arg("labels_b") = py::none(),
+        "gather + RandomResizedCrop (train) or central crop of center_frac + bilinear resize to out_h x out_w + "
+        "flip + normalize one batch (NHWC fp32, 3 channels); crops (int32 [batch, 5]) receives {top, left, h, w, "
+        "flip} per image; idx, nbatches, labels and the mix arguments as augment (the CutMix box in output pixels)");
+  m.def("rrc_params", &rrc_params, py::arg("seed"), py::arg("first_counter"), py::arg("n"), py::arg("B"),
+        py::arg("scale"), py::arg("ratio"), py::arg("H"), py::arg("W"),
+        "int32 [n, B, 4]: the windows {top, left, h, w} augment_resize draws at step counters first_counter .. "
+        "first_counter + n - 1");
   m.def("counter_inc", &counter_inc);
   m.def("stack_mean", &stack_mean);
   m.def("scale_", &scale_);

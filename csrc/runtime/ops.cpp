@@ -2414,6 +2414,116 @@ at::Tensor mix_params(int64_t seed, int64_t first_counter, int64_t n, double mix
   return out;
 }
 
+namespace {
+RrcCfg rrc_cfg(const std::vector<double>& scale, const std::vector<double>& ratio, const char* op) {
+  TORCH_CHECK(scale.size() == 2 && ratio.size() == 2, op, ": scale and ratio are (lo, hi) pairs");
+  TORCH_CHECK(0.0 < scale[0] && scale[0] <= scale[1] && scale[1] <= 1.0, op,
+              ": 0 < scale_lo <= scale_hi <= 1 required. Got: ", scale[0], ", ", scale[1]);
+  TORCH_CHECK(0.0 < ratio[0] && ratio[0] <= ratio[1] && std::isfinite(ratio[1]), op,
+              ": 0 < ratio_lo <= ratio_hi required. Got: ", ratio[0], ", ", ratio[1]);
+  return RrcCfg{(float)scale[0], (float)scale[1], (float)std::log(ratio[0]), (float)std::log(ratio[1])};
+}
+}  // namespace
+at::Tensor augment_resize(const at::Tensor& images, const c10::optional<at::Tensor>& indices, int64_t idx_offset,
+                          int64_t batch, std::vector<double> mean, std::vector<double> std_, int64_t out_h,
+                          int64_t out_w, bool train, std::vector<double> scale, std::vector<double> ratio,
+                          double center_frac, bool flip, const c10::optional<at::Tensor>& counter, int64_t seed,
+                          c10::optional<at::Tensor> out, int64_t nbatches, const c10::optional<at::Tensor>& labels,
+                          const c10::optional<at::Tensor>& labels_out, const at::Tensor& crops, double mixup_alpha,
+                          double cutmix_alpha, double mix_prob, double mix_switch_prob,
+                          const c10::optional<at::Tensor>& mix, const c10::optional<at::Tensor>& labels_b) {
+  TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.dim() == 4 && images.is_contiguous(),
+              "augment_resize: images must be contiguous uint8 [N, H, W, C] on the GPU");
+  const int64_t H = images.size(1), W = images.size(2), C = images.size(3);
+  TORCH_CHECK(C == 3, "augment_resize: 3-channel images only. Got: ", C);
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 0x7fff && W <= 0x7fff, "augment_resize: 1 <= H, W < 32768");
+  TORCH_CHECK(out_h >= 1 && out_w >= 1 && out_h <= 0x7fff && out_w <= 0x7fff,
+              "augment_resize: 1 <= out_h, out_w < 32768. Got: ", out_h, ", ", out_w);
+  TORCH_CHECK(batch >= 1 && batch <= 65535, "augment_resize: 1 <= batch < 65536");
+  TORCH_CHECK(mean.size() >= 1 && std_.size() >= 1, "augment_resize: mean and std needed");
+  const RrcCfg rc = rrc_cfg(scale, ratio, "augment_resize");
+  TORCH_CHECK(center_frac > 0.0 && center_frac <= 1.0, "augment_resize: 0 < center_frac <= 1 required. Got: ",
+              center_frac);
+  at::Tensor o;
+  if (out.has_value() && out->defined()) o = *out;
+  else
+    o = at::empty({batch, C, out_h, out_w},
+                  images.options().dtype(at::kFloat).memory_format(at::MemoryFormat::ChannelsLast));
+  TORCH_CHECK(o.is_cuda() && o.device() == images.device() && o.scalar_type() == at::kFloat &&
+                  o.numel() >= batch * C * out_h * out_w,
+              "augment_resize: out must be a float32 tensor on the images' device holding the batch");
+  TORCH_CHECK(crops.is_cuda() && crops.device() == images.device() && crops.scalar_type() == at::kInt &&
+                  crops.is_contiguous() && crops.dim() == 2 && crops.size(0) == batch && crops.size(1) == kCropRow,
+              "augment_resize: crops must be a contiguous int32 [batch, 5] tensor on the images' device");
+  float m[3], is[3];
+  for (int i = 0; i < 3; ++i) {
+    m[i] = (float)mean[std::min<size_t>(i, mean.size() - 1)];
+    is[i] = (float)(1.0 / std_[std::min<size_t>(i, std_.size() - 1)]);
+  }
+  const long long* ip = nullptr;
+  if (indices.has_value() && indices->defined()) {
+    TORCH_CHECK(indices->device() == images.device() && indices->scalar_type() == at::kLong && indices->is_contiguous(),
+                "augment_resize: indices must be a contiguous int64 tensor on the images' device");
+    TORCH_CHECK(idx_offset >= 0 && idx_offset + std::max<int64_t>(nbatches, 1) * batch <= indices->numel(),
+                "augment_resize: idx_offset + max(nbatches, 1) * batch = ",
+                idx_offset + std::max<int64_t>(nbatches, 1) * batch, " exceeds the ", indices->numel(), " indices");
+    ip = reinterpret_cast<const long long*>(indices->data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(idx_offset >= 0 && idx_offset + std::max<int64_t>(nbatches, 1) * batch <= images.size(0),
+                "augment_resize: the batch range exceeds the ", images.size(0), " images");
+  }
+  const long long* cp = nullptr;
+  if (counter.has_value() && counter->defined()) {
+    TORCH_CHECK(counter->device() == images.device() && counter->scalar_type() == at::kLong && counter->numel() >= 1,
+                "augment_resize: counter must be an int64 tensor on the images' device");
+    cp = reinterpret_cast<const long long*>(counter->data_ptr<int64_t>());
+  }
+  TORCH_CHECK(nbatches >= 0 && (nbatches == 0 || cp), "augment_resize: counter-driven batch offsets need the counter");
+  const long long* lp = nullptr;
+  long long* lo = nullptr;
+  if (labels_out.has_value() && labels_out->defined()) {
+    TORCH_CHECK(labels.has_value() && labels->defined() && labels->scalar_type() == at::kLong &&
+                    labels_out->scalar_type() == at::kLong && labels_out->numel() >= batch,
+                "augment_resize: labels / labels_out must be int64, labels_out holding the batch");
+    TORCH_CHECK(labels->device() == images.device() && labels_out->device() == images.device() &&
+                    labels->numel() >= images.size(0) && labels->is_contiguous() && labels_out->is_contiguous(),
+                "augment_resize: labels (one per image) and labels_out must be contiguous on the images' device");
+    lp = reinterpret_cast<const long long*>(labels->data_ptr<int64_t>());
+    lo = reinterpret_cast<long long*>(labels_out->data_ptr<int64_t>());
+  }
+  const MixCfg cfg = mix_cfg(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, "augment_resize");
+  float* mixp = nullptr;
+  long long* lb = nullptr;
+  if (mix_enabled(cfg)) {
+    TORCH_CHECK(mix.has_value() && mix->defined() && mix->device() == images.device() &&
+                    mix->scalar_type() == at::kFloat && mix->numel() >= kMixRow && mix->is_contiguous(),
+                "augment_resize: mixing needs mix, a contiguous float32 tensor of 8 on the images' device");
+    mixp = mix->data_ptr<float>();
+    if (labels_b.has_value() && labels_b->defined()) {
+      TORCH_CHECK(lp && labels_b->device() == images.device() && labels_b->scalar_type() == at::kLong &&
+                      labels_b->numel() >= batch && labels_b->is_contiguous(),
+                  "augment_resize: labels_b needs labels / labels_out and must be a contiguous int64 tensor holding "
+                  "the batch");
+      lb = reinterpret_cast<long long*>(labels_b->data_ptr<int64_t>());
+    }
+  }
+  augment_resize_launch(images.data_ptr<uint8_t>(), ip, idx_offset, (int)batch, (int)H, (int)W, (int)C, (int)out_h,
+                        (int)out_w, m, is, train, rc, center_frac, flip, cp, (unsigned long long)seed,
+                        o.data_ptr<float>(), cur_stream(), nbatches, lp, lo, crops.data_ptr<int>(), cfg, mixp, lb);
+  return o;
+}
+
+at::Tensor rrc_params(int64_t seed, int64_t first_counter, int64_t n, int64_t B, std::vector<double> scale,
+                      std::vector<double> ratio, int64_t H, int64_t W) {
+  TORCH_CHECK(n >= 0 && B >= 0 && H >= 1 && W >= 1 && H <= 0x7fff && W <= 0x7fff,
+              "rrc_params: n, B >= 0, 1 <= H, W < 32768");
+  const RrcCfg rc = rrc_cfg(scale, ratio, "rrc_params");
+  at::Tensor out = at::empty({n, B, 4}, at::TensorOptions().dtype(at::kInt).device(at::kCUDA));
+  rrc_params_launch((unsigned long long)seed, first_counter, n, (int)B, rc, (int)H, (int)W, out.data_ptr<int>(),
+                    cur_stream());
+  return out;
+}
+
 void counter_inc(at::Tensor c) { counter_inc_launch(reinterpret_cast<long long*>(c.data_ptr<int64_t>()), cur_stream()); }
 
 // ---------------------------------------------------------------- misc
