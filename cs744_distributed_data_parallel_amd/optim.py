@@ -32,6 +32,16 @@ load and store. ``d`` and ``1 - d`` live on the device (``set_ema_decay``), so a
 a decay warm-up without re-capture. A step skipped by ``skip_nonfinite`` leaves ``e`` unchanged, as
 does a step for a parameter without a gradient. ``ema_weights()`` swaps ``e`` into the model for
 evaluation; BatchNorm running statistics are not averaged (they are a moving average already).
+
+Learning-rate schedule (``lr_schedule``, an :class:`LRSchedule`): the rate of step ``t`` is
+``float32(base * f(t))`` with ``f`` a warm-up into a constant, cosine, polynomial or multi-step phase and
+``base`` what the step would use otherwise (``param_groups[i]["lr"]`` / ``lr_tensor``). The fused kernels
+evaluate ``f`` themselves in their prologue from a device step counter and advance that counter in the
+same launch (an arrival count over the workgroups), so the schedule costs no launch, needs no host value
+and a captured step changes its own rate at every replay. ``schedule_step``, ``last_lr``,
+``set_schedule_step``, ``set_lr_schedule`` and ``lr_schedule_table`` are the handles; ``state_dict()``
+carries the step as ``param_groups[i]["lr_schedule_step"]``. One schedule for all param groups; a step
+skipped by ``skip_nonfinite`` still counts (the schedule counts iterations).
 """
 from __future__ import annotations
 
@@ -43,6 +53,98 @@ from torch.optim import Optimizer
 
 from . import _native
 from .utils.arena import arena_for
+
+
+_LR_KINDS = {"constant": 0, "cosine": 1, "poly": 2, "step": 3}
+_LR_MAX_MILESTONES = 8
+
+
+class LRSchedule:
+    """A learning-rate factor ``f(t)`` of the step index ``t >= 0`` (the number of ``step()`` calls so far),
+    for ``SGD(..., lr_schedule=...)`` / ``LARS(..., lr_schedule=...)``:
+
+    * ``t < warmup_steps``: ``f = s + (1 - s) * t / warmup_steps``, ``s = warmup_start_factor`` (linear
+      warm-up, Goyal et al.);
+    * afterwards, with ``u = (t - warmup_steps) / (total_steps - warmup_steps)``:
+      ``constant``: 1; ``cosine``: ``r + (1 - r) * (1 + cos(pi u)) / 2``; ``poly``: ``r + (1 - r) * (1 - u) ** power``
+      (1: linear decay, 2: the LARS paper's); both are ``r = end_factor`` itself from ``total_steps`` on;
+      ``step``: ``gamma ** k``, ``k`` the number of ``milestones <= t``.
+
+    Everything is evaluated in fp64; :meth:`factor` is the formula in Python floats (what the CPU and
+    reference paths use), the fused kernels evaluate the same one on the device. The defaults are the
+    conventional ones; nothing was measured to choose them."""
+
+    def __init__(self, kind: str = "cosine", total_steps: int | None = None, warmup_steps: int = 0,
+                 warmup_start_factor: float = 0.0, end_factor: float = 0.0, power: float = 2.0,
+                 milestones=(), gamma: float = 0.1):
+        if kind not in _LR_KINDS:
+            raise ValueError(f"Invalid lr schedule kind: {kind!r} (one of {', '.join(_LR_KINDS)})")
+        if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+            raise ValueError(f"Invalid warmup_steps: {warmup_steps}")
+        s = float(warmup_start_factor)
+        if math.isnan(s) or not 0.0 <= s <= 1.0:
+            raise ValueError(f"Invalid warmup_start_factor: {warmup_start_factor}")
+        if kind in ("cosine", "poly"):
+            if total_steps is None or int(total_steps) != total_steps or not total_steps > warmup_steps:
+                raise ValueError(f"Invalid total_steps: {total_steps} ({kind} needs total_steps > warmup_steps)")
+        elif total_steps is not None and (int(total_steps) != total_steps or total_steps < 0):
+            raise ValueError(f"Invalid total_steps: {total_steps}")
+        if not float(end_factor) >= 0.0 or math.isinf(float(end_factor)):
+            raise ValueError(f"Invalid end_factor: {end_factor}")
+        if not float(power) > 0.0 or math.isinf(float(power)):
+            raise ValueError(f"Invalid power: {power}")
+        if not float(gamma) > 0.0 or math.isinf(float(gamma)):
+            raise ValueError(f"Invalid gamma: {gamma}")
+        ms = list(milestones)
+        if len(ms) > _LR_MAX_MILESTONES:
+            raise ValueError(f"Invalid milestones: at most {_LR_MAX_MILESTONES}, got {len(ms)}")
+        if any(int(m) != m or m < 0 for m in ms) or any(b <= a for a, b in zip(ms, ms[1:])):
+            raise ValueError(f"Invalid milestones: {milestones} (non-negative integers, strictly increasing)")
+        self.kind = kind
+        self.total_steps = int(total_steps) if total_steps is not None else 0
+        self.warmup_steps = int(warmup_steps)
+        self.warmup_start_factor = s
+        self.end_factor = float(end_factor)
+        self.power = float(power)
+        self.milestones = tuple(int(m) for m in ms)
+        self.gamma = float(gamma)
+
+    def factor(self, t: int) -> float:
+        t = int(t)
+        if t < 0:
+            raise ValueError(f"Invalid step index: {t}")
+        W, T = self.warmup_steps, self.total_steps
+        if t < W:
+            s = self.warmup_start_factor
+            return s + (1.0 - s) * t / W
+        if self.kind in ("cosine", "poly"):
+            r = self.end_factor
+            if t >= T:
+                return r
+            u = (t - W) / (T - W)
+            if self.kind == "cosine":
+                return r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * u))
+            return r + (1.0 - r) * math.pow(1.0 - u, self.power)
+        if self.kind == "step":
+            f = 1.0
+            for m in self.milestones:
+                if m <= t:
+                    f *= self.gamma
+            return f
+        return 1.0
+
+    def rate(self, base: float, t: int) -> float:
+        """``float32(base * factor(t))`` as a Python float: the rate of step ``t``."""
+        return torch.tensor(float(base) * self.factor(t), dtype=torch.float64).to(torch.float32).item()
+
+    def _pack_args(self):
+        return (_LR_KINDS[self.kind], self.warmup_steps, self.warmup_start_factor, self.total_steps, self.end_factor,
+                self.power, list(self.milestones), self.gamma)
+
+    def __repr__(self):
+        return (f"LRSchedule(kind={self.kind!r}, total_steps={self.total_steps}, warmup_steps={self.warmup_steps}, "
+                f"warmup_start_factor={self.warmup_start_factor}, end_factor={self.end_factor}, power={self.power}, "
+                f"milestones={self.milestones}, gamma={self.gamma})")
 
 
 class SGD(Optimizer):
@@ -60,6 +162,7 @@ class SGD(Optimizer):
         max_grad_norm: float | None = None,
         skip_nonfinite: bool = False,
         ema_decay: float | None = None,
+        lr_schedule: LRSchedule | None = None,
     ):
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -73,6 +176,8 @@ class SGD(Optimizer):
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
         if ema_decay is not None:
             _check_ema_decay(ema_decay)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise TypeError(f"lr_schedule must be an LRSchedule, not {type(lr_schedule).__name__}")
         defaults = dict(
             lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
             maximize=maximize, foreach=None, differentiable=False, fused=None,
@@ -122,6 +227,23 @@ class SGD(Optimizer):
             self._ema_decay = float(ema_decay)
             self.set_ema_decay(ema_decay)
             self.reset_ema()
+        # learning-rate schedule: an optimizer attribute again; None allocates nothing
+        self._lr_schedule = None
+        self._sched_state = self._sched_last = self._sched_cfg = None
+        self._sched_pending = False  # this step()'s advance of t, until a launch (or the fallback) takes it
+        self._sched_take = False  # whether the group being stepped holds the step()'s last launch
+        self._sched_gi = 0  # the group being stepped
+        self._sched_host = None  # (t, factor) of this step() where a reference path asked for the rate
+        if lr_schedule is not None and all_params:
+            dev = all_params[0].device
+            # allocated here, never inside a capture: {t, arrivals}, the rate of the last step and, on the
+            # GPU, the configuration the kernels read
+            self._sched_state = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._sched_last = torch.zeros(1, dtype=torch.float32, device=dev)
+            if dev.type == "cuda" and _native.available():
+                self._sched_cfg = torch.zeros(128, dtype=torch.uint8, device=dev)
+            self._lr_schedule = lr_schedule
+            self.set_lr_schedule(lr_schedule)
 
     # ------------------------------------------------------------------ gradient clipping
     @property
@@ -210,6 +332,11 @@ class SGD(Optimizer):
         super().load_state_dict(state_dict)
         self._adopt_momentum()
         self._adopt_ema()
+        # the schedule's step: applied when the state carries it, t left alone when it does not; never a
+        # live param_groups entry
+        ts = [g.pop("lr_schedule_step") for g in self.param_groups if "lr_schedule_step" in g]
+        if ts and self._lr_schedule is not None:
+            self.set_schedule_step(int(ts[0]))
 
     def _adopt_momentum(self):
         """Loaded momentum buffers are fresh tensors, while a replayed hipGraph step reads and writes
@@ -226,6 +353,118 @@ class SGD(Optimizer):
                 if b is not None and b.data_ptr() != views[p._cdp_index].data_ptr():
                     views[p._cdp_index].copy_(b)
                     st["momentum_buffer"] = views[p._cdp_index]
+
+    # ------------------------------------------------------------------ learning-rate schedule
+    @property
+    def lr_schedule(self):
+        """The :class:`LRSchedule` as last set; None when the optimizer has none."""
+        return self._lr_schedule
+
+    @property
+    def schedule_step(self):
+        """The schedule's step index ``t`` (the ``step()`` calls so far): a 0-dim int64 device view the
+        fused step advances itself (reading it here never syncs); None without ``lr_schedule``."""
+        return self._sched_state[0] if self._sched_state is not None else None
+
+    @property
+    def last_lr(self):
+        """The rate of the last step for param group 0 (0-dim float32 device view); None without
+        ``lr_schedule``."""
+        return self._sched_last[0] if self._sched_last is not None else None
+
+    def _sched_check(self, what):
+        if self._lr_schedule is None:
+            raise RuntimeError(f"{what}: the optimizer was built without lr_schedule")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what} writes or reads the schedule's device words: not while the stream is capturing")
+
+    def set_schedule_step(self, t: int):
+        """Continue the schedule from step ``t`` (also zeroes the arrival word of the fused step's
+        advance): in place, so a captured step follows at its next replay. Not while capturing."""
+        self._sched_check("set_schedule_step")
+        if int(t) != t or t < 0:
+            raise ValueError(f"Invalid schedule step: {t}")
+        self._sched_state[0:1].fill_(int(t))
+        self._sched_state[1:2].fill_(0)
+
+    def set_lr_schedule(self, sched: LRSchedule):
+        """Replace the schedule of an optimizer built with one: the device configuration is refilled in
+        place, so a captured step uses the new schedule at its next replay; ``t`` stays. Not while
+        capturing."""
+        self._sched_check("set_lr_schedule")
+        if not isinstance(sched, LRSchedule):
+            raise TypeError(f"lr_schedule must be an LRSchedule, not {type(sched).__name__}")
+        self._lr_schedule = sched
+        if self._sched_cfg is not None:
+            self._sched_cfg.copy_(_native.lib().lr_sched_pack(*sched._pack_args()))
+
+    def lr_schedule_table(self, first: int, n: int) -> torch.Tensor:
+        """float32 ``[n]``: the rates of steps ``first .. first + n - 1`` for param group 0 at its current
+        base rate (``lr_tensor`` when there is one), as the fused step evaluates them (on the device
+        where the parameters are; from :meth:`LRSchedule.factor` otherwise)."""
+        if self._lr_schedule is None:
+            raise RuntimeError("lr_schedule_table: the optimizer was built without lr_schedule")
+        if first < 0 or n < 0:
+            raise ValueError(f"lr_schedule_table: first >= 0 and n >= 0 required, got {first}, {n}")
+        base = self.param_groups[0]["lr"]
+        if self._sched_cfg is not None and not _native.force_reference():
+            return _native.lib().lr_sched_table(self._sched_cfg, self._lr_tensor, base, int(first), int(n))
+        return torch.tensor([self._lr_schedule.rate(base, first + i) for i in range(n)], dtype=torch.float32,
+                            device=self._sched_last.device)
+
+    def _sched_kw(self, advance: bool) -> dict:
+        """The schedule block of one fused launch; ``advance``: it is the last launch of this step()."""
+        if self._sched_cfg is None:
+            return {}
+        # last_lr is group 0's rate: only its launches record theirs
+        return dict(sched_state=self._sched_state, sched_cfg=self._sched_cfg,
+                    sched_last=self._sched_last if self._sched_gi == 0 else None, sched_advance=bool(advance))
+
+    def _sched_take_advance(self) -> bool:
+        """True once per step(), for the launch that advances t: only in the last group with work."""
+        if self._sched_pending and self._sched_take:
+            self._sched_pending = False
+            return True
+        return False
+
+    def _lr_of(self, group) -> float:
+        """The rate of this step for ``group`` on the reference paths (CPU, ``force_reference``,
+        per-parameter torch ops): ``group["lr"]``, or with a schedule ``float32(lr * factor(t))`` with t
+        read on the host."""
+        if self._lr_schedule is None:
+            return group["lr"]
+        if self._sched_host is None:
+            if self._sched_state.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("lr_schedule: this step runs on a reference path, which reads the schedule's "
+                                   "step on the host: not while the stream is capturing")
+            t = int(self._sched_state[0])
+            self._sched_host = (t, self._lr_schedule.factor(t))
+        return torch.tensor(float(group["lr"]) * self._sched_host[1], dtype=torch.float64).to(torch.float32).item()
+
+    def _sched_finish_step(self):
+        """The advance of t when no fused launch took it (nothing launched, reference paths)."""
+        if not self._sched_pending:
+            return
+        self._sched_pending = False
+        st = self._sched_state
+        if self._sched_host is None and self._sched_cfg is not None and not _native.force_reference():
+            _native.lib().lr_sched_advance(st, self._sched_cfg, self._sched_last, self._lr_tensor,
+                                           self.param_groups[0]["lr"])
+            return
+        self._sched_last.fill_(self._lr_of(self.param_groups[0]))
+        st[0:1] += 1
+        st[1:2].fill_(0)
+
+    def state_dict(self):
+        """torch's, and with a schedule ``param_groups[i]["lr_schedule_step"] = t`` (one host read: not
+        while capturing). The extra key is inert in ``torch.optim.SGD.load_state_dict``."""
+        sd = super().state_dict()
+        if self._lr_schedule is not None:
+            self._sched_check("state_dict")
+            t = int(self._sched_state[0])
+            for g in sd["param_groups"]:
+                g["lr_schedule_step"] = t
+        return sd
 
     # ------------------------------------------------------------------ weight EMA
     @property
@@ -393,6 +632,8 @@ class SGD(Optimizer):
             if done:
                 raise RuntimeError(f"overlapped optimizer step: only {done} of {ov['n']} buckets were stepped")
         self._counter_pending = self._step_counter
+        self._sched_pending = self._lr_schedule is not None
+        self._sched_host = None
         skip = False
         self._clip_fused = False
         if self._clip_enabled:
@@ -403,10 +644,16 @@ class SGD(Optimizer):
                 with_grad = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
                 skip = bool(with_grad) and self._clip_reference(with_grad)
         self._begin_step()
+        last_gi = -1
+        if self._sched_pending and not skip:
+            last_gi = max((gi for gi, g in enumerate(self.param_groups) if any(p.grad is not None for p in g["params"])),
+                          default=-1)
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
             if not params or skip:
                 continue
+            self._sched_take = gi == last_gi  # the step()'s last launch advances the schedule
+            self._sched_gi = gi
             if self._arena is not None:
                 self._arena.prep_valid = None  # re-marked below only by a fused step
             if params[0].is_cuda and not _native.force_reference():
@@ -420,6 +667,7 @@ class SGD(Optimizer):
             else:
                 c += 1
             self._counter_pending = None
+        self._sched_finish_step()  # no fused launch took it (nothing launched / reference paths)
         self._steps += 1
         self._run_post_step_joins()
         return loss
@@ -451,8 +699,8 @@ class SGD(Optimizer):
         bucket for the reducer's ``set_bucket_step`` -- the SGD of that range, run on the reducer's
         step stream right after the bucket's all-reduce -- or None when the step cannot be split
         this iteration (several param groups, parameters outside one arena run, first and later
-        momentum steps mixed, no native kernels, ``max_grad_norm`` / ``skip_nonfinite`` or ``ema_decay``
-        set: the step then runs whole at ``step()``). The next ``step()`` then only does the
+        momentum steps mixed, no native kernels, ``max_grad_norm`` / ``skip_nonfinite``, ``ema_decay`` or
+        ``lr_schedule`` set: the step then runs whole at ``step()``). The next ``step()`` then only does the
         bookkeeping, provided the reducer stepped every bucket; hyperparameters are those at the
         time of this call (the forward), the first-step momentum rule (buf = d_p) is kept."""
         if self._arena is None or len(self.param_groups) != 1 or _native.force_reference():
@@ -461,6 +709,8 @@ class SGD(Optimizer):
             return None  # the clip needs the norm of the whole model: the step runs whole at step()
         if self._ema_decay is not None:
             return None  # the per-bucket launches carry no EMA: the step runs whole at step()
+        if self._lr_schedule is not None:
+            return None  # the per-bucket launches carry no schedule: the step runs whole at step()
         group = self.param_groups[0]
         params, arena = group["params"], self._arena
         if len(params) != len(arena.params) or any(not p.is_cuda for p in params):
@@ -568,10 +818,12 @@ class SGD(Optimizer):
         # general path: one launch per parameter (non-arena / partial groups)
         if self._clip_fused:
             raise RuntimeError("gradient clipping was planned into a flat step that did not run")
-        for p in params:
+        for k, p in enumerate(params):
             st = self.state[p]
             buf = st.get("momentum_buffer")
             first = buf is None
+            # the schedule: every launch reads t, the last one of the step() advances it
+            sched = self._sched_kw(k == len(params) - 1 and self._sched_take_advance())
             if m != 0.0 and first:
                 buf = torch.empty_like(p, memory_format=torch.contiguous_format)
             pv = p.data if p.data.is_contiguous() else None
@@ -587,13 +839,13 @@ class SGD(Optimizer):
                 gc = g.contiguous()
                 bc = buf.contiguous() if buf is not None else None
                 C.sgd_step(pc.view(-1), gc.view(-1), bc.view(-1) if bc is not None else None, lr_t, lr, m, damp, wd,
-                           1.0, nest, first, maxim, **ema)
+                           1.0, nest, first, maxim, **ema, **sched)
                 p.data.copy_(pc)
                 if buf is not None and bc is not buf:
                     buf.copy_(bc)
             else:
                 C.sgd_step(pv.view(-1), g.view(-1), buf.view(-1) if buf is not None else None, lr_t, lr, m, damp,
-                           wd, 1.0, nest, first, maxim, **ema)
+                           wd, 1.0, nest, first, maxim, **ema, **sched)
             if eb is not None and ec is not eb:
                 eb.copy_(ec)
             if m != 0.0:
@@ -617,6 +869,11 @@ class SGD(Optimizer):
         ema = arena.ema_buffer() if self._ema_decay is not None else None  # state[p]["ema_buffer"] are its views
         if ema is not None:
             clip.update(ema=ema[s:e], ema_coef=self._ema_coef)
+        adv = self._sched_take_advance()
+        if plan is not None and "subs" in plan:
+            clip.update(self._sched_kw(False))  # several launches: only the last advances t (below)
+        else:
+            clip.update(self._sched_kw(adv))
         if plan is None:
             C.sgd_step(arena.data[s:e], arena.grad[s:e], mom, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, ctr,
                        **clip)
@@ -629,6 +886,8 @@ class SGD(Optimizer):
                 ck = clip if k == last or not clip else dict(clip, stats=None)  # stats written once
                 if ema is not None:
                     ck = dict(ck, ema=ema[a:b])
+                if adv and k == last:
+                    ck = dict(ck, sched_advance=True)
                 if sub is None:
                     C.sgd_step(arena.data[a:b], arena.grad[a:b], mk, lr_t, lr, m, damp, wd, 1.0, nest, first, maxim, c,
                                **ck)
@@ -651,7 +910,7 @@ class SGD(Optimizer):
 
     def _apply_reference(self, group, p, d_p):
         """Momentum, dampening, Nesterov and ``p -= lr * d_p`` for one parameter, with torch ops."""
-        lr, m, damp = group["lr"], group["momentum"], group["dampening"]
+        lr, m, damp = self._lr_of(group), group["momentum"], group["dampening"]
         if m != 0:
             st = self.state[p]
             buf = st.get("momentum_buffer")
@@ -678,9 +937,9 @@ class LARS(SGD):
     and decayed when ``w.ndim > 1`` or ``exclude_bias_and_norm`` is false; with the default exclusion
     biases and BatchNorm weights get ``q = 1`` and no weight decay (the usual recipe), so the whole
     model stays one param group and one flat launch. Momentum, dampening, Nesterov, ``maximize``,
-    ``max_grad_norm`` / ``skip_nonfinite``, ``ema_decay`` and the device-side learning rate (warm-up
-    through ``lr_tensor``) are :class:`SGD`'s. ``trust_coefficient``, ``eps`` and ``exclude_bias_and_norm``
-    are ``param_groups`` entries. The defaults 0.001 and 1e-8 are the conventional ones of the paper
+    ``max_grad_norm`` / ``skip_nonfinite``, ``ema_decay``, ``lr_schedule`` (warm-up and polynomial decay
+    evaluated inside the step) and the device-side base rate (``lr_tensor``) are :class:`SGD`'s.
+    ``trust_coefficient``, ``eps`` and ``exclude_bias_and_norm`` are ``param_groups`` entries. The defaults 0.001 and 1e-8 are the conventional ones of the paper
     and common implementations; nothing was measured to choose them.
 
     MI355X path, where the step is one flat launch over an arena range (the conditions of the fused
@@ -710,6 +969,7 @@ class LARS(SGD):
         max_grad_norm: float | None = None,
         skip_nonfinite: bool = False,
         ema_decay: float | None = None,
+        lr_schedule: LRSchedule | None = None,
     ):
         if not float(trust_coefficient) >= 0.0:
             raise ValueError(f"Invalid trust_coefficient: {trust_coefficient}")
@@ -718,7 +978,8 @@ class LARS(SGD):
         self._extra_defaults = dict(trust_coefficient=float(trust_coefficient), eps=float(eps),
                                     exclude_bias_and_norm=bool(exclude_bias_and_norm))
         super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, maximize=maximize, flat=flat,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
+                         lr_schedule=lr_schedule)
         all_params = [p for g in self.param_groups for p in g["params"]]
         self._slot = {id(p): k for k, p in enumerate(all_params)}
         # allocated here, never inside a capture
@@ -749,7 +1010,8 @@ class LARS(SGD):
 
     def bucket_steps(self, ranges, reducer):
         """None: the per-bucket split of an overlapped step is not offered (the norms are local to a
-        parameter, so it is possible; until then the step runs whole at ``step()``)."""
+        parameter, so it is possible; until then the step runs whole at ``step()``), with or without an
+        ``lr_schedule``."""
         return None
 
     def _begin_step(self):

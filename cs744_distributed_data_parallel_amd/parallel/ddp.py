@@ -112,7 +112,9 @@ class DistributedDataParallel(nn.Module):
         ``clip_grad_norm_``, ...) is not seen by an overlapped step: its SGD has already run inside
         backward. An ``SGD`` built with ``max_grad_norm`` or ``skip_nonfinite`` needs the norm of
         the whole model, so it declines the split and its step runs whole at ``step()``, after the
-        last all-reduce."""
+        last all-reduce. So does one built with ``ema_decay`` or ``lr_schedule``: the per-bucket
+        launches carry neither the EMA nor the schedule (whose step index the last launch of a
+        ``step()`` advances), so the step runs whole at ``step()``."""
         if not hasattr(optimizer, "bucket_steps"):
             raise TypeError("overlap_optimizer needs cs744_distributed_data_parallel_amd.SGD")
         self._step_opt = optimizer

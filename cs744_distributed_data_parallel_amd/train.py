@@ -30,7 +30,7 @@ from . import distributed as dist
 from .data import MIX_MODES, DeviceLoader, DistributedSampler, MixTarget, cifar10_binary, synthetic_cifar10, synthetic_imagenet
 from .models import get_model
 from .ops import CrossEntropyLoss, count_correct
-from .optim import LARS, SGD
+from .optim import LARS, SGD, LRSchedule
 from .parallel import (
     BucketedOverlap,
     DistributedDataParallel,
@@ -104,6 +104,13 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 tr = optimizer.trust_ratios
                 print("[cdp] rank {}: trust ratio in iter {} is min {} max {}".format(
                     rank, iter_number, float(tr.min()), float(tr.max())), file=sys.stderr)
+            if getattr(optimizer, "last_lr", None) is not None:
+                # learning-rate schedule: the rate of the window's last step, and the step index the next
+                # one will use (stderr, as above)
+                import sys
+
+                print("[cdp] rank {}: lr in iter {} is {} (schedule step {})".format(
+                    rank, iter_number, float(optimizer.last_lr), int(optimizer.schedule_step)), file=sys.stderr)
             if isinstance(target, MixTarget):
                 # mixup / CutMix: the window's last mix, as the loader's kernel published it (stderr, as above)
                 import sys
@@ -202,14 +209,15 @@ def run(rank, size, epochs, batch_size, args):
         model = DistributedDataParallel(model, bucket_cap_mb=args.bucket_cap_mb)
     elif strategy == "bucketed_overlap":
         sync = BucketedOverlap(model, bucket_cap_mb=args.bucket_cap_mb)
+    lr_schedule = _lr_schedule_from(args, epochs, len(train_loader))
     if args.optimizer == "lars":
         optimizer = LARS(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
                          trust_coefficient=args.trust_coefficient, max_grad_norm=args.clip_grad_norm,
-                         skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay)
+                         skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay, lr_schedule=lr_schedule)
     else:
         optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
                         max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite,
-                        ema_decay=args.ema_decay)
+                        ema_decay=args.ema_decay, lr_schedule=lr_schedule)
 
     start_epoch = 0
     if args.resume and args.checkpoint_dir:
@@ -253,6 +261,23 @@ def run(rank, size, epochs, batch_size, args):
                                                                  os.path.splitext(args.trace)[1] or ".json")
         trace.dump(path)
     return model
+
+
+def _lr_schedule_from(args, epochs, loader_len):
+    """The ``--lr-schedule`` flags as an :class:`LRSchedule` over the whole run (None without them):
+    ``total_steps = epochs * iterations per epoch``, milestones given in epochs. ``--warmup-iters``
+    alone means a constant schedule behind the warm-up. ``--resume`` continues it from the checkpoint's
+    step (the optimizer's ``state_dict`` carries it)."""
+    kind = args.lr_schedule
+    if kind is None:
+        if not args.warmup_iters:
+            return None
+        kind = "constant"
+    per_epoch = min(loader_len, args.iters) if args.iters is not None else loader_len
+    return LRSchedule(kind, total_steps=epochs * per_epoch, warmup_steps=args.warmup_iters,
+                      warmup_start_factor=args.warmup_start_factor, end_factor=args.lr_end_factor,
+                      power=args.poly_power, milestones=[e * per_epoch for e in args.lr_milestones],
+                      gamma=args.lr_gamma)
 
 
 def _reducer_of(model, sync):
@@ -318,6 +343,20 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=256, help="global batch (split int(B/W) per rank)")
     p.add_argument("--lr", type=float, default=0.1)
     p.add_argument("--iters", type=int, default=None, help="max iterations per epoch")
+    p.add_argument("--lr-schedule", default=None, choices=["constant", "cosine", "poly", "step"],
+                   help="scale --lr by a schedule evaluated inside the fused optimizer step, over epochs x iterations "
+                        "per epoch steps (default: none, every step at --lr)")
+    p.add_argument("--warmup-iters", type=int, default=0, metavar="N",
+                   help="linear warm-up over the first N steps (alone: a constant schedule behind it)")
+    p.add_argument("--warmup-start-factor", type=float, default=0.0, metavar="F",
+                   help="the warm-up starts at F x --lr")
+    p.add_argument("--lr-end-factor", type=float, default=0.0, metavar="F",
+                   help="cosine / poly end at F x --lr")
+    p.add_argument("--poly-power", type=float, default=2.0, metavar="P",
+                   help="power of --lr-schedule poly (1: linear decay, 2: the LARS paper's)")
+    p.add_argument("--lr-milestones", type=int, nargs="+", default=[], metavar="E",
+                   help="epochs at which --lr-schedule step multiplies the rate by --lr-gamma")
+    p.add_argument("--lr-gamma", type=float, default=0.1, metavar="G", help="factor of --lr-schedule step")
     p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
                    help="sgd (the reference's) or lars: SGD with layer-wise adaptive rate scaling, for large batches")
     p.add_argument("--trust-coefficient", type=float, default=0.001, metavar="FLOAT",

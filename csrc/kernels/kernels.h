@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lars.h"
+#include "lr_sched.h"
 #include "mix.h"
 #include "rrc.h"
 
@@ -184,11 +185,24 @@ struct EmaArgs {
   float* e = nullptr;
   const float* coef = nullptr;
 };
+// Learning-rate schedule of a fused SGD step (lr_sched.h): state == nullptr: off, the kernels run the
+// instantiations without it. Otherwise state = {t, arrivals} (int64, device), cfg the device-side
+// configuration, and every workgroup steps at lr_t = float32(double(base) * f(t)) with base the rate it
+// would use otherwise; workgroup 0 writes lr_t to last_lr (optional). advance != 0 (the last launch of a
+// step()): the launch also stores t + 1, by an arrival count over its workgroups (sched_arrive,
+// misc.hip); advance == 0: the launch only reads t.
+struct SchedArgs {
+  long long* state = nullptr;
+  const LrSchedCfg* cfg = nullptr;
+  float* last_lr = nullptr;
+  int advance = 0;
+};
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
                      bool maximize, hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{},
-                     const LarsArgs& lars = LarsArgs{}, const EmaArgs& ema = EmaArgs{});
+                     const LarsArgs& lars = LarsArgs{}, const EmaArgs& ema = EmaArgs{},
+                     const SchedArgs& sched = SchedArgs{});
 void slab_sum_launch(const float* slab, int S, long long n, float* dst, bool accumulate, hipStream_t st);
 void slab_sum_strided_launch(const float* slab, int S, long long n_src, int src_cols, int dst_cols, float* dst,
                              bool accumulate, hipStream_t st);
@@ -294,7 +308,16 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
                 hipStream_t st, long long* counter = nullptr, const ClipArgs& clip = ClipArgs{},
-                const LarsArgs& lars = LarsArgs{}, const EmaArgs& ema = EmaArgs{});
+                const LarsArgs& lars = LarsArgs{}, const EmaArgs& ema = EmaArgs{},
+                const SchedArgs& sched = SchedArgs{});
+// workgroups of sgd_launch over n floats without LARS (the arrivals of a scheduled step's count)
+int sgd_grid(long long n);
+// The schedule's step without an SGD launch (a step() that launches nothing): one thread stores t + 1,
+// zeroes the arrival word and writes lr_t of step t to last_lr (optional)
+void lr_sched_advance_launch(const SchedArgs& sched, const float* lr_ptr, float lr, hipStream_t st);
+// out[i] = lr_t of step first + i, i < n: the rates the SGD kernels use at those steps
+void lr_sched_table_launch(const LrSchedCfg* cfg, const float* lr_ptr, float lr, long long first, long long n,
+                           float* out, hipStream_t st);
 
 // grad_norm.hip: the global gradient norm of a flat fp32 range, in two deterministic stages.
 // grad_sumsq_launch writes P = grad_norm_parts(n) fp64 partial sums of squares, workgroup b over the

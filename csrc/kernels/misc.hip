@@ -380,11 +380,44 @@ __device__ __forceinline__ void sgd_lars_prologue(const LarsArgs& lars, const La
   wd = (lars.exclude && !pr.matrix ? 0.f : wd) * q;
 }
 
-template <bool CLIP, bool LARS, bool EMA>
+// Learning-rate schedule (SCHED instantiations only; SchedArgs in kernels.h, lr_sched.h). Thread 0 of the
+// workgroup loads t and the configuration, evaluates lr_t in fp64 and shares it through LDS (one
+// barrier); every workgroup of every launch of a step gets the same bits. It keeps t for sched_arrive;
+// workgroup 0 records the rate (last_lr is read by no launch).
+__device__ __forceinline__ float sgd_sched_prologue(const SchedArgs& sched, float base, float* s_lr, long long& t) {
+  if (threadIdx.x == 0) {
+    t = sched.state[0];
+    const float lr = lr_sched_rate(*sched.cfg, t, base);
+    *s_lr = lr;
+    if (blockIdx.x == 0 && sched.last_lr) sched.last_lr[0] = lr;
+  }
+  __syncthreads();
+  return *s_lr;
+}
+// The advance of t (the last launch of a step: sched.advance). Every workgroup must see the same t, so
+// nobody may store t + 1 while another workgroup can still load t. The thread that loaded t arrives at
+// the end of its workgroup's work, on every exit path, with one relaxed, agent-scope, returning integer
+// add on the arrival word; the thread that draws the last ticket knows that every other workgroup has
+// loaded t already, stores t + 1 and zeroes the arrival word for the next launch.
+// Nothing inside the launch reads those stores (the next launch sees them across the kernel
+// boundary), so there is no fence. Integer tickets leave the step bitwise reproducible: whoever is
+// last stores the same values.
+typedef __attribute__((address_space(1))) long long glb_i64;
+__device__ __forceinline__ void sched_arrive(const SchedArgs& sched, long long t) {
+  if (threadIdx.x != 0 || !sched.advance) return;
+  const long long ticket =
+      __hip_atomic_fetch_add((glb_i64*)(sched.state + 1), 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket == (long long)gridDim.x - 1) {
+    sched.state[0] = t + 1;
+    sched.state[1] = 0;
+  }
+}
+
+template <bool CLIP, bool LARS, bool EMA, bool SCHED>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                  long long n, const float* __restrict__ lr_ptr, float lr_host, float m,
                                                  float damp, float wd, float gs, int flags, long long* counter,
-                                                 ClipArgs clip, LarsArgs lars, EmaArgs ema) {
+                                                 ClipArgs clip, LarsArgs lars, EmaArgs ema, SchedArgs sched) {
   const bool nesterov = flags & 1, first = flags & 2, maximize = flags & 4, has_mom = flags & 8;
   const float ed = EMA ? ema.coef[0] : 0.f, eomd = EMA ? ema.coef[1] : 0.f;
   // a data loader's step counter advanced by the step (one dispatch less per step; the counter is
@@ -392,7 +425,12 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   if (counter && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1;
   bool skip = false;
   if (CLIP) skip = sgd_clip_prologue(clip, gs);
-  const float lr = lr_ptr ? lr_ptr[0] : lr_host;
+  float lr = lr_ptr ? lr_ptr[0] : lr_host;
+  long long sched_t = 0;  // (thread 0 of the SCHED instantiations)
+  if (SCHED) {
+    __shared__ float s_lr;
+    lr = sgd_sched_prologue(sched, lr, &s_lr, sched_t);
+  }
   if (LARS) {
     // one workgroup per (parameter, chunk) item of the norms pass's work list: whole float4s of one
     // parameter, so the ratio is workgroup-uniform
@@ -416,6 +454,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
         st4(ema.e + e, ev);
       }
     }
+    if (SCHED) sched_arrive(sched, sched_t);
     return;
   }
   const long long n4 = n >> 2;
@@ -446,6 +485,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     if (has_mom) buf[i] = bb;
     if (EMA && !(CLIP && skip)) ema.e[i] = ema_one(ema.e[i], pp, ed, eomd);
   }
+  if (SCHED) sched_arrive(sched, sched_t);
 }
 
 // ------------------------------------------------------------------ weight maxima
@@ -481,14 +521,14 @@ __device__ __forceinline__ void tile_max_store(const unsigned* s, float* __restr
 // EMA: the weight average e (EmaArgs) is updated from the new p on every path. The tile paths load e
 // only after p and buf have left, into the registers of g and buf: measured with the compiler's
 // report, +2 to +3 VGPRs over the EMA = false instantiation, which is the kernel without this block.
-template <bool CLIP, bool LARS, bool EMA>
+template <bool CLIP, bool LARS, bool EMA, bool SCHED>
 __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ buf, const SgdPrepSeg* __restrict__ segs,
                                                       int nseg, int nblk_w, const SgdPrepChunk* __restrict__ chunks,
                                                       float* __restrict__ part, const float* __restrict__ lr_ptr,
                                                       float lr_host, float m, float damp, float wd, float gs,
                                                       int flags, long long* counter, ClipArgs clip, LarsArgs lars,
-                                                      EmaArgs ema) {
+                                                      EmaArgs ema, SchedArgs sched) {
   // taps per group: 3 x 3 float4 in flight per thread keeps the kernel near 64 VGPRs (8 waves per
   // SIMD for this bandwidth-bound pass; a whole 3x3 filter per group held 256 VGPRs, 1 wave per SIMD)
   constexpr int TG = 3;
@@ -498,7 +538,12 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
   bool skip = false;
   if (CLIP) skip = sgd_clip_prologue(clip, gs);  // as sgd_kernel; the |max| / W^T below are of the unchanged p
   const bool nesterov = flags & 1, first = flags & 2, maximize = flags & 4, has_mom = flags & 8;
-  const float lr = lr_ptr ? lr_ptr[0] : lr_host;
+  float lr = lr_ptr ? lr_ptr[0] : lr_host;
+  long long sched_t = 0;  // as sgd_kernel
+  if (SCHED) {
+    __shared__ float s_lr;
+    lr = sgd_sched_prologue(sched, lr, &s_lr, sched_t);
+  }
   const float ed = EMA ? ema.coef[0] : 0.f, eomd = EMA ? ema.coef[1] : 0.f;
   const int b = blockIdx.x;
   if (b >= nblk_w) {
@@ -524,6 +569,7 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
         st4(ema.e + e, ev);
       }
     }
+    if (SCHED) sched_arrive(sched, sched_t);
     return;
   }
   int si = 0;
@@ -687,6 +733,7 @@ __global__ __launch_bounds__(256) void sgd_prep_kernel(float* __restrict__ p, co
   }
   __syncthreads();
   tile_max_store(smax, part + sg.pofs, Co, Ci, co0, ci0);
+  if (SCHED) sched_arrive(sched, sched_t);
 }
 
 // ------------------------------------------------------------------ augmentation
@@ -1025,6 +1072,22 @@ __global__ __launch_bounds__(256) void rrc_params_kernel(unsigned long long seed
 }
 
 __global__ void counter_inc_kernel(long long* c) { c[0] += 1; }
+// The schedule's step without an SGD launch: one thread does what the last arrival of sched_arrive does.
+__global__ void lr_sched_advance_kernel(SchedArgs sched, const float* __restrict__ lr_ptr, float lr_host) {
+  const long long t = sched.state[0];
+  const float lr = lr_sched_rate(*sched.cfg, t, lr_ptr ? lr_ptr[0] : lr_host);
+  sched.state[0] = t + 1;
+  sched.state[1] = 0;
+  if (sched.last_lr) sched.last_lr[0] = lr;
+}
+// out[i] = lr_t of step first + i, i < n (the rates sgd_sched_prologue gives at those steps): the
+// schedule's counterpart of mix_params_kernel / rrc_params_kernel
+__global__ __launch_bounds__(256) void lr_sched_table_kernel(const LrSchedCfg* __restrict__ cfg,
+                                                            const float* __restrict__ lr_ptr, float lr_host,
+                                                            long long first, long long n, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = lr_sched_rate(*cfg, first + i, lr_ptr ? lr_ptr[0] : lr_host);
+}
 
 // dX of a stride-2 conv's sub-pixel parity classes with no filter taps (bit 2 ph + pw of mask):
 // zeros, float4 along C (NHWC), one thread per float4 of the classes' pixels
@@ -1574,6 +1637,8 @@ __global__ __launch_bounds__(256) void wtrans_sub_kernel(const float* __restrict
 }
 }  // namespace
 
+int sgd_grid(long long n) { return grid_for((n + 3) / 4); }
+
 void xent_fwd_launch(const float* logits, const long long* tgt, int B, int C, float* loss, long long* correct,
                      float* sum_out, hipStream_t st, float eps, int topk, const long long* tgt_b, const float* lam) {
   if (!(eps >= 0.f && eps <= 1.f) || topk < 1) throw std::runtime_error("xent_fwd: label smoothing in [0, 1], topk >= 1");
@@ -1600,21 +1665,44 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
                     : (eps != 0.f ? xent_bwd_kernel<true, false> : xent_bwd_kernel<false, false>);
   hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, st, logits, tgt, gscale, B, C, dlogits, eps, tgt_b, lam);
 }
+void lr_sched_advance_launch(const SchedArgs& sched, const float* lr_ptr, float lr, hipStream_t st) {
+  if (!sched.state || !sched.cfg) throw std::runtime_error("lr_sched_advance: state and cfg required");
+  hipLaunchKernelGGL(lr_sched_advance_kernel, dim3(1), dim3(1), 0, st, sched, lr_ptr, lr);
+}
+void lr_sched_table_launch(const LrSchedCfg* cfg, const float* lr_ptr, float lr, long long first, long long n,
+                           float* out, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(lr_sched_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cfg, lr_ptr, lr, first,
+                     n, out);
+}
+// The SGD kernels come in 16 instantiations each: CLIP x LARS x EMA x SCHED. SCHED is a template
+// parameter like the others, so that the instantiations without it are the code they were before it
+// existed (no LDS word, no barrier, no branch).
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
-                hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars, const EmaArgs& ema) {
+                hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars, const EmaArgs& ema,
+                const SchedArgs& sched) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
   if ((ema.e != nullptr) != (ema.coef != nullptr)) throw std::runtime_error("sgd: ema and ema_coef go together");
-  if (lars.params && lars.nitems < 1) return;
+  if ((sched.state != nullptr) != (sched.cfg != nullptr)) throw std::runtime_error("sgd: sched state and cfg go together");
+  if (lars.params && lars.nitems < 1) {
+    if (sched.state && sched.advance) lr_sched_advance_launch(sched, lr_ptr, lr, st);  // a step all the same
+    return;
+  }
   // LARS: one workgroup per item of the work list, which tiles [0, n)
   const dim3 grid(lars.params ? lars.nitems : grid_for((n + 3) / 4));
-#define CDP_SGD(CLIP, LARS, EMA)                                                                                  \
-  hipLaunchKernelGGL((sgd_kernel<CLIP, LARS, EMA>), grid, dim3(256), 0, st, p, g, buf, n, lr_ptr, lr, momentum,  \
-                     dampening, wd, grad_scale, flags, counter, clip, lars, ema)
-#define CDP_SGD_E(CLIP, LARS)             \
-  do {                                    \
-    if (ema.e) CDP_SGD(CLIP, LARS, true); \
-    else CDP_SGD(CLIP, LARS, false);      \
+#define CDP_SGD(CLIP, LARS, EMA, SCHED)                                                                               \
+  hipLaunchKernelGGL((sgd_kernel<CLIP, LARS, EMA, SCHED>), grid, dim3(256), 0, st, p, g, buf, n, lr_ptr, lr, momentum, \
+                     dampening, wd, grad_scale, flags, counter, clip, lars, ema, sched)
+#define CDP_SGD_S(CLIP, LARS, EMA)                   \
+  do {                                               \
+    if (sched.state) CDP_SGD(CLIP, LARS, EMA, true); \
+    else CDP_SGD(CLIP, LARS, EMA, false);            \
+  } while (0)
+#define CDP_SGD_E(CLIP, LARS)               \
+  do {                                      \
+    if (ema.e) CDP_SGD_S(CLIP, LARS, true); \
+    else CDP_SGD_S(CLIP, LARS, false);      \
   } while (0)
   if (lars.params) {
     if (clip.part) CDP_SGD_E(true, true);
@@ -1624,20 +1712,30 @@ void sgd_launch(float* p, const float* g, float* buf, long long n, const float* 
     else CDP_SGD_E(false, false);
   }
 #undef CDP_SGD_E
+#undef CDP_SGD_S
 #undef CDP_SGD
 }
 void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* segs, int nseg, int nblk_w,
                      const SgdPrepChunk* chunks, int nchunk, float* wmax, const float* lr_ptr, float lr,
                      float momentum, float dampening, float wd, float grad_scale, bool nesterov, bool first,
                      bool maximize, hipStream_t st, long long* counter, const ClipArgs& clip, const LarsArgs& lars,
-                     const EmaArgs& ema) {
+                     const EmaArgs& ema, const SchedArgs& sched) {
   const int flags = (nesterov ? 1 : 0) | (first ? 2 : 0) | (maximize ? 4 : 0) | (momentum != 0.f ? 8 : 0);
   if ((ema.e != nullptr) != (ema.coef != nullptr)) throw std::runtime_error("sgd: ema and ema_coef go together");
-  if (nblk_w + nchunk <= 0) return;
-#define CDP_SGD_PREP_E(CLIP, LARS, EMA)                                                                             \
-  hipLaunchKernelGGL((sgd_prep_kernel<CLIP, LARS, EMA>), dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, segs, \
-                     nseg, nblk_w, chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags, counter,  \
-                     clip, lars, ema)
+  if ((sched.state != nullptr) != (sched.cfg != nullptr)) throw std::runtime_error("sgd: sched state and cfg go together");
+  if (nblk_w + nchunk <= 0) {
+    if (sched.state && sched.advance) lr_sched_advance_launch(sched, lr_ptr, lr, st);  // a step all the same
+    return;
+  }
+#define CDP_SGD_PREP_S(CLIP, LARS, EMA, SCHED)                                                                      \
+  hipLaunchKernelGGL((sgd_prep_kernel<CLIP, LARS, EMA, SCHED>), dim3(nblk_w + nchunk), dim3(256), 0, st, p, g, buf, \
+                     segs, nseg, nblk_w, chunks, wmax, lr_ptr, lr, momentum, dampening, wd, grad_scale, flags,      \
+                     counter, clip, lars, ema, sched)
+#define CDP_SGD_PREP_E(CLIP, LARS, EMA)                   \
+  do {                                                    \
+    if (sched.state) CDP_SGD_PREP_S(CLIP, LARS, EMA, true); \
+    else CDP_SGD_PREP_S(CLIP, LARS, EMA, false);          \
+  } while (0)
 #define CDP_SGD_PREP(CLIP, LARS)                 \
   do {                                           \
     if (ema.e) CDP_SGD_PREP_E(CLIP, LARS, true); \
@@ -1652,6 +1750,7 @@ void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* seg
   }
 #undef CDP_SGD_PREP
 #undef CDP_SGD_PREP_E
+#undef CDP_SGD_PREP_S
 }
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,

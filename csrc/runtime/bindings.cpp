@@ -120,7 +120,18 @@ PYBIND11_MODULE(_C, m) {
         py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("grad_scale"), py::arg("nesterov"),
         py::arg("first"), py::arg("maximize"), py::arg("counter") = py::none(), py::arg("clip_part") = py::none(),
         py::arg("max_norm") = 0.0, py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false,
-        py::arg("lars") = LarsStep{}, py::arg("ema") = py::none(), py::arg("ema_coef") = py::none());
+        py::arg("lars") = LarsStep{}, py::arg("ema") = py::none(), py::arg("ema_coef") = py::none(),
+        py::arg("sched_state") = py::none(), py::arg("sched_cfg") = py::none(), py::arg("sched_last") = py::none(),
+        py::arg("sched_advance") = false);
+  m.def("lr_sched_pack", &lr_sched_pack, py::arg("kind"), py::arg("warmup_steps"), py::arg("warmup_start_factor"),
+        py::arg("total_steps"), py::arg("end_factor"), py::arg("power"), py::arg("milestones"), py::arg("gamma"),
+        "the learning-rate schedule's configuration as CPU bytes (kind: 0 constant, 1 cosine, 2 poly, 3 step)");
+  m.def("lr_sched_table", &lr_sched_table, py::arg("cfg"), py::arg("lr_t"), py::arg("lr"), py::arg("first"),
+        py::arg("n"), "float32 [n]: the rates the fused step uses at schedule steps first .. first + n - 1");
+  m.def("lr_sched_advance", &lr_sched_advance, py::arg("state"), py::arg("cfg"), py::arg("last") = py::none(),
+        py::arg("lr_t") = py::none(), py::arg("lr") = 0.0,
+        "one step of the schedule without an SGD launch (a step() that launches nothing)");
+  m.def("sgd_grid", &sgd_grid_, py::arg("n"), "workgroups of the flat sgd_step launch over n floats");
   m.def("grad_norm_parts", &grad_norm_parts_, py::arg("n"), "partials grad_sumsq writes for a range of n floats");
   m.def("grad_norm_chunk", &grad_norm_chunk_, py::arg("n"), "floats of the range each grad_sumsq workgroup owns");
   m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("part"),
@@ -136,7 +147,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("first"), py::arg("maximize"), py::arg("desc"), py::arg("meta"), py::arg("amax"),
         py::arg("counter") = py::none(), py::arg("clip_part") = py::none(), py::arg("max_norm") = 0.0,
         py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false, py::arg("lars") = LarsStep{},
-        py::arg("ema") = py::none(), py::arg("ema_coef") = py::none(),
+        py::arg("ema") = py::none(), py::arg("ema_coef") = py::none(), py::arg("sched_state") = py::none(),
+        py::arg("sched_cfg") = py::none(), py::arg("sched_last") = py::none(), py::arg("sched_advance") = false,
         "SGD over an arena range that also emits the next step's weight |max| / W^T");
   m.def("augment", &augment, py::arg("images"), py::arg("indices"), py::arg("idx_offset"), py::arg("batch"),
         py::arg("mean"), py::arg("std"), py::arg("pad"), py::arg("flip"), py::arg("counter"), py::arg("seed"),

@@ -1993,7 +1993,76 @@ EmaArgs ema_args(const c10::optional<at::Tensor>& ema, const c10::optional<at::T
   a.coef = ema_coef->data_ptr<float>();
   return a;
 }
+const LrSchedCfg* sched_cfg_ptr(const at::Tensor& cfg, const at::Device& dev) {
+  TORCH_CHECK(cfg.is_cuda() && cfg.device() == dev && cfg.scalar_type() == at::kByte && cfg.is_contiguous() &&
+                  cfg.numel() >= (int64_t)sizeof(LrSchedCfg) && (reinterpret_cast<uintptr_t>(cfg.data_ptr()) & 7) == 0,
+              "lr schedule: sched_cfg must be lr_sched_pack's bytes on the parameters' device");
+  return reinterpret_cast<const LrSchedCfg*>(cfg.data_ptr<uint8_t>());
+}
+// the learning-rate schedule block of a fused SGD launch: sched_state = {t, arrivals} (int64), sched_cfg the
+// bytes of lr_sched_pack on the device, sched_last (optional) one float that receives the step's rate
+SchedArgs sched_args(const c10::optional<at::Tensor>& state, const c10::optional<at::Tensor>& cfg,
+                     const c10::optional<at::Tensor>& last, bool advance, const at::Device& dev) {
+  SchedArgs a;
+  const bool has_s = state.has_value() && state->defined(), has_c = cfg.has_value() && cfg->defined();
+  const bool has_l = last.has_value() && last->defined();
+  TORCH_CHECK(has_s == has_c, "sgd: sched_state and sched_cfg go together");
+  TORCH_CHECK(has_s || (!has_l && !advance), "sgd: sched_last / sched_advance need sched_state and sched_cfg");
+  if (!has_s) return a;
+  TORCH_CHECK(state->is_cuda() && state->device() == dev && state->scalar_type() == at::kLong &&
+                  state->is_contiguous() && state->numel() >= 2,
+              "sgd: sched_state must be a contiguous int64 device tensor {t, arrivals}");
+  a.state = reinterpret_cast<long long*>(state->data_ptr<int64_t>());
+  a.cfg = sched_cfg_ptr(*cfg, dev);
+  if (has_l) {
+    TORCH_CHECK(last->is_cuda() && last->device() == dev && last->scalar_type() == at::kFloat && last->numel() >= 1,
+                "sgd: sched_last must be a float32 device tensor");
+    a.last_lr = last->data_ptr<float>();
+  }
+  a.advance = advance ? 1 : 0;
+  return a;
+}
 }  // namespace
+
+// ---------------------------------------------------------------- learning-rate schedule
+at::Tensor lr_sched_pack(int64_t kind, int64_t warmup_steps, double warmup_start_factor, int64_t total_steps,
+                         double end_factor, double power, const std::vector<int64_t>& milestones, double gamma) {
+  TORCH_CHECK(kind >= kLrConstant && kind <= kLrStep, "lr_sched_pack: unknown kind ", kind);
+  TORCH_CHECK(warmup_steps >= 0 && warmup_start_factor >= 0.0 && warmup_start_factor <= 1.0,
+              "lr_sched_pack: warmup_steps >= 0 and warmup_start_factor in [0, 1]");
+  TORCH_CHECK((kind != kLrCosine && kind != kLrPoly) || total_steps > warmup_steps,
+              "lr_sched_pack: total_steps > warmup_steps required");
+  TORCH_CHECK(end_factor >= 0.0 && power > 0.0 && gamma > 0.0, "lr_sched_pack: end_factor >= 0, power > 0, gamma > 0");
+  TORCH_CHECK((int64_t)milestones.size() <= kLrMaxMilestones, "lr_sched_pack: at most ", kLrMaxMilestones, " milestones");
+  LrSchedCfg c{};
+  c.kind = kind, c.warmup_steps = warmup_steps, c.total_steps = total_steps;
+  c.nmilestones = (long long)milestones.size();
+  for (size_t i = 0; i < milestones.size(); ++i) {
+    TORCH_CHECK(i == 0 || milestones[i] > milestones[i - 1], "lr_sched_pack: milestones must be strictly increasing");
+    c.milestones[i] = milestones[i];
+  }
+  c.warmup_start_factor = warmup_start_factor, c.end_factor = end_factor, c.power = power, c.gamma = gamma;
+  at::Tensor out = at::empty({(int64_t)sizeof(LrSchedCfg)}, at::TensorOptions().dtype(at::kByte));
+  std::memcpy(out.data_ptr<uint8_t>(), &c, sizeof(LrSchedCfg));
+  return out;
+}
+
+at::Tensor lr_sched_table(const at::Tensor& cfg, const c10::optional<at::Tensor>& lr_t, double lr, int64_t first,
+                          int64_t n) {
+  TORCH_CHECK(first >= 0 && n >= 0, "lr_sched_table: first >= 0 and n >= 0");
+  const LrSchedCfg* c = sched_cfg_ptr(cfg, cfg.device());
+  at::Tensor out = at::empty({n}, at::TensorOptions().dtype(at::kFloat).device(cfg.device()));
+  lr_sched_table_launch(c, fptr(lr_t), (float)lr, first, n, out.data_ptr<float>(), cur_stream());
+  return out;
+}
+
+void lr_sched_advance(at::Tensor state, const at::Tensor& cfg, const c10::optional<at::Tensor>& last,
+                      const c10::optional<at::Tensor>& lr_t, double lr) {
+  const SchedArgs sa = sched_args(state, cfg, last, true, state.device());
+  lr_sched_advance_launch(sa, fptr(lr_t), (float)lr, cur_stream());
+}
+
+int64_t sgd_grid_(int64_t n) { return sgd_grid(n); }
 
 // ---------------------------------------------------------------- LARS
 namespace {
@@ -2182,10 +2251,13 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
               bool maximize, const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
               double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite, const LarsStep& lars,
-              const c10::optional<at::Tensor>& ema, const c10::optional<at::Tensor>& ema_coef) {
+              const c10::optional<at::Tensor>& ema, const c10::optional<at::Tensor>& ema_coef,
+              const c10::optional<at::Tensor>& sched_state, const c10::optional<at::Tensor>& sched_cfg,
+              const c10::optional<at::Tensor>& sched_last, bool sched_advance) {
   const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
   const EmaArgs ea = ema_args(ema, ema_coef, p);
+  const SchedArgs sa = sched_args(sched_state, sched_cfg, sched_last, sched_advance, p.device());
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
   float* bp = nullptr;
   if (momentum != 0.0) {
@@ -2199,7 +2271,7 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
   }
   sgd_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, p.numel(), fptr(lr_t), (float)lr, (float)momentum,
              (float)dampening, (float)wd, (float)grad_scale, nesterov, first, maximize, cur_stream(),
-             counter_ptr(counter), clip, la, ea);
+             counter_ptr(counter), clip, la, ea, sa);
 }
 
 // ---------------------------------------------------------------- SGD + next-step weight preparation
@@ -2298,10 +2370,13 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
                    const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
                    double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite,
                    const LarsStep& lars, const c10::optional<at::Tensor>& ema,
-                   const c10::optional<at::Tensor>& ema_coef) {
+                   const c10::optional<at::Tensor>& ema_coef, const c10::optional<at::Tensor>& sched_state,
+                   const c10::optional<at::Tensor>& sched_cfg, const c10::optional<at::Tensor>& sched_last,
+                   bool sched_advance) {
   const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, p);
   check_f32_cuda(p, "param");
   const EmaArgs ea = ema_args(ema, ema_coef, p);
+  const SchedArgs sa = sched_args(sched_state, sched_cfg, sched_last, sched_advance, p.device());
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && p.numel() == g.numel(), "sgd: flat contiguous tensors required");
   float* bp = nullptr;
   if (momentum != 0.0) {
@@ -2322,7 +2397,8 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
   sgd_prep_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, reinterpret_cast<const SgdPrepSeg*>(d), nseg, nblk,
                   reinterpret_cast<const SgdPrepChunk*>(d + nseg * sizeof(SgdPrepSeg)), nchunk,
                   amax.data_ptr<float>(), fptr(lr_t), (float)lr, (float)momentum, (float)dampening, (float)wd,
-                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter), clip, la, ea);
+                  (float)grad_scale, nesterov, first, maximize, cur_stream(), counter_ptr(counter), clip, la, ea,
+                  sa);
 }
 
 // ---------------------------------------------------------------- data augmentation

@@ -116,14 +116,33 @@ void sgd_step_prep(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> 
                    double max_norm = 0.0, const c10::optional<at::Tensor>& stats = c10::nullopt,
                    bool skip_nonfinite = false, const LarsStep& lars = LarsStep{},
                    const c10::optional<at::Tensor>& ema = c10::nullopt,
-                   const c10::optional<at::Tensor>& ema_coef = c10::nullopt);
+                   const c10::optional<at::Tensor>& ema_coef = c10::nullopt,
+                   const c10::optional<at::Tensor>& sched_state = c10::nullopt,
+                   const c10::optional<at::Tensor>& sched_cfg = c10::nullopt,
+                   const c10::optional<at::Tensor>& sched_last = c10::nullopt, bool sched_advance = false);
 void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, const c10::optional<at::Tensor>& lr_t,
               double lr, double momentum, double dampening, double wd, double grad_scale, bool nesterov, bool first,
               bool maximize, const c10::optional<at::Tensor>& counter,
               const c10::optional<at::Tensor>& clip_part = c10::nullopt, double max_norm = 0.0,
               const c10::optional<at::Tensor>& stats = c10::nullopt, bool skip_nonfinite = false,
               const LarsStep& lars = LarsStep{}, const c10::optional<at::Tensor>& ema = c10::nullopt,
-              const c10::optional<at::Tensor>& ema_coef = c10::nullopt);
+              const c10::optional<at::Tensor>& ema_coef = c10::nullopt,
+              const c10::optional<at::Tensor>& sched_state = c10::nullopt,
+              const c10::optional<at::Tensor>& sched_cfg = c10::nullopt,
+              const c10::optional<at::Tensor>& sched_last = c10::nullopt, bool sched_advance = false);
+// Learning-rate schedule of the fused step (csrc/kernels/lr_sched.h). sched_state = {t, arrivals} (int64,
+// device), sched_cfg = lr_sched_pack's bytes moved to the device, sched_last = one float32 that receives the
+// rate of the launch (optional); sched_advance: this launch is the last of its step() and stores t + 1.
+// lr_sched_pack: the configuration as CPU bytes (kind: 0 constant, 1 cosine, 2 poly, 3 step).
+at::Tensor lr_sched_pack(int64_t kind, int64_t warmup_steps, double warmup_start_factor, int64_t total_steps,
+                         double end_factor, double power, const std::vector<int64_t>& milestones, double gamma);
+// float32 [n]: the rates of steps first .. first + n - 1 for the base rate (lr_t ? lr_t[0] : lr)
+at::Tensor lr_sched_table(const at::Tensor& cfg, const c10::optional<at::Tensor>& lr_t, double lr, int64_t first,
+                          int64_t n);
+// one step of the schedule without an SGD launch: last = rate of step t, t += 1, arrivals = 0
+void lr_sched_advance(at::Tensor state, const at::Tensor& cfg, const c10::optional<at::Tensor>& last,
+                      const c10::optional<at::Tensor>& lr_t, double lr);
+int64_t sgd_grid_(int64_t n);  // workgroups of the flat sgd_step launch over n floats
 // gradient-norm clipping over a flat fp32 range (csrc/kernels/grad_norm.hip): part[0 .. grad_norm_parts(n))
 // fp64 partial sums of squares; clip_scale: g *= min(max_norm / (norm + 1e-6), 1), stats = {norm, coef, -}
 int64_t grad_norm_parts_(int64_t n);
