@@ -42,6 +42,11 @@ and a captured step changes its own rate at every replay. ``schedule_step``, ``l
 ``set_schedule_step``, ``set_lr_schedule`` and ``lr_schedule_table`` are the handles; ``state_dict()``
 carries the step as ``param_groups[i]["lr_schedule_step"]``. One schedule for all param groups; a step
 skipped by ``skip_nonfinite`` still counts (the schedule counts iterations).
+
+:class:`AdamW` and :class:`LAMB` are the Adam family over the same arenas, with the same options under the
+same names: ``exp_avg`` in the momentum storage, ``exp_avg_sq`` in a second one beside it, the step count of
+the bias corrections in a device word that the fused kernel (``csrc/kernels/adam.hip``) reads and advances
+itself. They do not emit the next forward's weight preparation; see the classes.
 """
 from __future__ import annotations
 
@@ -52,7 +57,7 @@ import torch
 from torch.optim import Optimizer
 
 from . import _native
-from .utils.arena import arena_for
+from .utils.arena import _view_like, arena_for
 
 
 _LR_KINDS = {"constant": 0, "cosine": 1, "poly": 2, "step": 3}
@@ -172,18 +177,27 @@ class SGD(Optimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
-            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
-        if ema_decay is not None:
-            _check_ema_decay(ema_decay)
-        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
-            raise TypeError(f"lr_schedule must be an LRSchedule, not {type(lr_schedule).__name__}")
+        self._check_common(max_grad_norm, ema_decay, lr_schedule)
         defaults = dict(
             lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
             maximize=maximize, foreach=None, differentiable=False, fused=None,
         )
         defaults.update(getattr(self, "_extra_defaults", {}))  # a subclass's own param_group entries (LARS)
         super().__init__(params, defaults)
+        self._init_common(flat, max_grad_norm, skip_nonfinite, ema_decay, lr_schedule)
+
+    @staticmethod
+    def _check_common(max_grad_norm, ema_decay, lr_schedule):
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        if ema_decay is not None:
+            _check_ema_decay(ema_decay)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise TypeError(f"lr_schedule must be an LRSchedule, not {type(lr_schedule).__name__}")
+
+    def _init_common(self, flat, max_grad_norm, skip_nonfinite, ema_decay, lr_schedule):
+        """What every optimizer of the family sets up after ``Optimizer.__init__``: the arena, the clip's,
+        the EMA's and the schedule's device words (SGD / LARS here, AdamW / LAMB below)."""
         # callables run at the end of every step (DistributedDataParallel.early_buffer_broadcast
         # joins its end-of-backward buffer broadcast here, after the SGD it overlaps)
         self._post_step_joins = []
@@ -205,7 +219,7 @@ class SGD(Optimizer):
         self.skip_nonfinite = bool(skip_nonfinite)
         self._clip_part = self._clip_stats = None
         self._clip_fused = False
-        if self.skip_nonfinite and any(g["dampening"] != 0 for g in self.param_groups):
+        if self.skip_nonfinite and any(g.get("dampening", 0) != 0 for g in self.param_groups):
             # a skipped first momentum step zeroes the buffer and the next computes
             # buf = (1 - dampening) * d_p: torch's first-step buf = d_p only for dampening 0
             raise ValueError("skip_nonfinite requires zero dampening")
@@ -284,7 +298,7 @@ class SGD(Optimizer):
             return False
         if any(getattr(p, "_cdp_arena", None) is not self._arena for p in params):
             return False
-        if group["momentum"] != 0.0:
+        if group.get("momentum", 0.0) != 0.0:  # (the Adam family has no first-step rule)
             firsts = self._first_flags(params)
             if any(firsts) and not all(firsts):
                 return False
@@ -667,6 +681,7 @@ class SGD(Optimizer):
             else:
                 c += 1
             self._counter_pending = None
+        self._end_step(skip)
         self._sched_finish_step()  # no fused launch took it (nothing launched / reference paths)
         self._steps += 1
         self._run_post_step_joins()
@@ -674,6 +689,10 @@ class SGD(Optimizer):
 
     def _begin_step(self):
         """Per-step planning of a subclass, after the clip's and before the first group's launch."""
+
+    def _end_step(self, skipped: bool):
+        """Per-step bookkeeping of a subclass, after the last group's launch (``skipped``: the up-front clip
+        of the reference paths left the step out)."""
 
     def _flat_step_extra(self, C, arena, s, e, plan) -> dict:
         """Further launches before, and keyword arguments of, the flat step's kernel (LARS)."""
@@ -1080,6 +1099,353 @@ class LARS(SGD):
                 self._trust[k].fill_(1.0)
                 d_p = g if not group["maximize"] else -g
             self._apply_reference(group, p, d_p)
+
+
+class AdamW(SGD):
+    """AdamW (decoupled weight decay, ``torch.optim.AdamW``'s semantics) over the flat arenas, with everything
+    the SGD family offers (``max_grad_norm`` / ``skip_nonfinite``, ``ema_decay``, ``lr_schedule``, ``lr_tensor``,
+    ``advance_each_step``, ``add_post_step_join``, the reducer's relayout) under the same names. For the step
+    count ``t`` (the steps taken so far) and ``T = t + 1``:
+
+        ``m = b1 m + (1 - b1) g``, ``v = b2 v + (1 - b2) g^2``,
+        ``a = (m / (1 - b1^T)) / (sqrt(v) / sqrt(1 - b2^T) + eps)``, ``w -= lr (a + wd w)``
+
+    (``w - lr (a + wd w)`` is torch's ``w (1 - lr wd) - lr a``). ``param_groups`` carry exactly the keys of the
+    installed ``torch.optim.AdamW`` and the per-parameter state is ``step``, ``exp_avg``, ``exp_avg_sq``, so
+    ``state_dict()`` loads into ``torch.optim.AdamW`` and the reverse (``ema_buffer`` and ``lr_schedule_step`` are
+    inert there). ``amsgrad`` is not built.
+
+    The step count lives on the device (``adam_step``, an int64 word allocated here): every workgroup of the
+    fused kernel (``csrc/kernels/adam.hip``) reads it in its prologue, evaluates the bias corrections in fp64
+    and the last launch of the step advances it by an arrival count, so a captured hipGraph step needs no host
+    value; ``set_adam_step`` refills it in place. All parameters share the one ``t`` -- unlike torch, where a
+    parameter without a gradient keeps its own count; ``state_dict()`` writes ``t`` into every ``step`` and
+    ``load_state_dict()`` raises ``ValueError`` when the loaded ones disagree. A step skipped by
+    ``skip_nonfinite`` leaves ``t``, ``m``, ``v``, ``w`` and the EMA bitwise unchanged (the learning-rate
+    schedule's own counter still counts the iteration).
+
+    ``exp_avg`` lives in the arena's momentum storage, ``exp_avg_sq`` in a second one beside it; one flat launch
+    moves 28 bytes per element (36 with the EMA). The step does not emit the next forward's weight maxima and
+    W^T as the fused SGD step does: the forward prepares its weights with its stand-alone launch (one more launch
+    and one more read of the conv weights per step). ``bucket_steps`` declines, so under
+    ``DistributedDataParallel.overlap_optimizer`` the step runs whole at ``step()``. CPU, ``force_reference``,
+    several param groups' odd layouts and parameters outside one arena run evaluate the same formulas per
+    parameter (torch ops, or one launch per parameter on the GPU). With ``eps = 0`` an element whose ``m`` and
+    ``v`` are both zero gets ``a = 0`` from the kernels (the arena's pad floats stay zero) and ``0 / 0`` from the
+    torch-op paths, as from torch."""
+
+    _lamb = False
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *,
+                 amsgrad: bool = False, maximize: bool = False, flat: bool = True, max_grad_norm: float | None = None,
+                 skip_nonfinite: bool = False, ema_decay: float | None = None, lr_schedule: LRSchedule | None = None):
+        if amsgrad:
+            raise ValueError("amsgrad=True is not built")
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("a tensor lr is not supported: lr_tensor() is the device-side rate")
+        # torch's own checks of lr, betas, eps and weight_decay (ValueError), and its param_group keys
+        probe = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=betas, eps=eps,
+                                  weight_decay=weight_decay, maximize=bool(maximize))
+        self._check_common(max_grad_norm, ema_decay, lr_schedule)
+        defaults = dict(probe.defaults)
+        defaults.update(getattr(self, "_extra_defaults", {}))  # a subclass's own param_group entries (LAMB)
+        Optimizer.__init__(self, params, defaults)
+        self._init_common(flat, max_grad_norm, skip_nonfinite, ema_decay, lr_schedule)
+        all_params = [p for g in self.param_groups for p in g["params"]]
+        # {t, arrivals}: allocated here, never inside a capture
+        self._adam_state = torch.zeros(2, dtype=torch.int64, device=all_params[0].device)
+        self._adam_host = None  # t of this step() where a reference path read it
+        self._adam_ref = self._adam_advanced = False
+        self._adam_last_gi = -1
+        self._lamb_fused = False
+
+    # ------------------------------------------------------------------ the step count
+    @property
+    def adam_step(self):
+        """The step count ``t`` (steps taken so far): a 0-dim int64 device view the fused step advances
+        itself; reading it here never syncs."""
+        return self._adam_state[0]
+
+    def set_adam_step(self, t: int):
+        """Continue from step count ``t`` (also zeroes the arrival word): in place, so a captured step follows
+        at its next replay. Not while capturing."""
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_adam_step fills the device step count: not while the stream is capturing")
+        if int(t) != t or t < 0:
+            raise ValueError(f"Invalid step count: {t}")
+        self._adam_state[0:1].fill_(int(t))
+        self._adam_state[1:2].fill_(0)
+
+    def _adam_t_host(self) -> int:
+        if self._adam_host is None:
+            if self._adam_state.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("this step runs on a reference path, which reads the step count on the host: "
+                                   "not while the stream is capturing")
+            self._adam_host = int(self._adam_state[0])
+        return self._adam_host
+
+    # ------------------------------------------------------------------ state
+    def _state_of(self, p):
+        """``state[p]`` with its moments: arena views where the parameter is in the arena (a tensor loaded
+        from elsewhere is copied in), fresh zeros otherwise."""
+        st = self.state[p]
+        a = self._arena
+        if a is not None and getattr(p, "_cdp_arena", None) is a:
+            off = a.offsets[p._cdp_index]
+            for key, buf in (("exp_avg", a.momentum_buffer()), ("exp_avg_sq", a.second_buffer())):
+                b = st.get(key)
+                if b is None or b.data_ptr() != buf.data_ptr() + off * buf.element_size():
+                    home = _view_like(buf, off, p.data)
+                    if b is not None:
+                        home.copy_(b)
+                    st[key] = home
+        else:
+            for key in ("exp_avg", "exp_avg_sq"):
+                if st.get(key) is None:
+                    st[key] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        if "step" not in st:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)  # state_dict() writes t here
+        return st
+
+    def _on_relayout(self, arena):
+        super()._on_relayout(arena)
+        self._lamb_plan = None  # offsets moved: LAMB's work list is stale
+        if arena is not self._arena:
+            return
+        mv = arena.momentum_views() if arena.momentum is not None else None
+        sv = arena.second_views() if arena.second is not None else None
+        for p in arena.params:
+            st = self.state.get(p)
+            if not st:
+                continue
+            if mv is not None and st.get("exp_avg") is not None:
+                st["exp_avg"] = mv[p._cdp_index]
+            if sv is not None and st.get("exp_avg_sq") is not None:
+                st["exp_avg_sq"] = sv[p._cdp_index]
+
+    def state_dict(self):
+        """torch's: ``step`` of every parameter is ``t`` as the float32 0-dim tensor ``torch.optim.AdamW`` uses
+        (one host read: not while capturing)."""
+        if self._adam_state.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("state_dict reads the device step count: not while the stream is capturing")
+        t = int(self._adam_state[0])
+        for g in self.param_groups:
+            for p in g["params"]:
+                st = self.state.get(p)
+                if st and "exp_avg" in st:
+                    st["step"] = torch.tensor(float(t), dtype=torch.float32)
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        steps = {int(float(st["step"])) for st in state_dict["state"].values() if "step" in st}
+        if len(steps) > 1:
+            raise ValueError(f"load_state_dict: the parameters' step counts disagree ({sorted(steps)}); "
+                             "all parameters share one step count here")
+        super().load_state_dict(state_dict)
+        if steps:
+            self.set_adam_step(steps.pop())
+        # loaded moments are fresh tensors, while a replayed hipGraph step reads the arena's storages: move
+        # them in now (as _adopt_momentum does for SGD); a parameter without loaded moments starts from zero
+        a = self._arena
+        with torch.no_grad():
+            for g in self.param_groups:
+                for p in g["params"]:
+                    st = self.state.get(p)
+                    if st and "exp_avg" in st:
+                        self._state_of(p)
+                    elif a is not None and getattr(p, "_cdp_arena", None) is a:
+                        if a.momentum is not None:
+                            a.momentum_views()[p._cdp_index].zero_()
+                        if a.second is not None:
+                            a.second_views()[p._cdp_index].zero_()
+
+    def bucket_steps(self, ranges, reducer):
+        """None: the per-bucket split of an overlapped step is not offered; the step runs whole at ``step()``."""
+        return None
+
+    # ------------------------------------------------------------------ step
+    def _begin_step(self):
+        self._adam_host = None
+        self._adam_ref = self._adam_advanced = False
+        self._adam_last_gi = max((gi for gi, g in enumerate(self.param_groups)
+                                  if any(p.grad is not None for p in g["params"])), default=-1)
+        if self._lamb:
+            self._lamb_fused = self._flat_fusable()
+            if self._lamb_fused and self._clip_enabled and not self._clip_fused:
+                self._lamb_fused = False  # the clip already scaled the gradients with torch ops
+
+    def _end_step(self, skipped):
+        # the advance of t when no fused launch took it (reference paths); a skipped step did not happen
+        if self._adam_ref and not self._adam_advanced and not skipped:
+            self._adam_state[0:1] += 1
+
+    def _step_native(self, gi, group, params):
+        if self._lamb and not self._lamb_fused:
+            return self._step_reference(group, params)  # the per-parameter launches know no trust ratio
+        C = _native.lib()
+        (b1, b2), eps, wd, maxim, lr = group["betas"], group["eps"], group["weight_decay"], group["maximize"], group["lr"]
+        lr_t = self._lr_tensor if (gi == 0 and self._lr_tensor is not None) else None
+        arena = self._arena
+        last = gi == self._adam_last_gi  # the step()'s last launch advances t
+        rng = None
+        if arena is not None and len(params) == len(group["params"]):
+            rng = arena.contiguous_range(params)
+        if rng is not None:
+            arena.ensure_grads_in_arena(params)
+            for p in params:
+                self._state_of(p)
+            s, e = rng
+            w, g = arena.data[s:e], arena.grad[s:e]
+            m, v = arena.momentum_buffer()[s:e], arena.second_buffer()[s:e]
+            ctr, self._counter_pending = self._counter_pending, None
+            kw = {}
+            if self._clip_fused:
+                # one extra dispatch, as in the SGD step: the partial sums of squares of the whole range
+                part = self._clip_part[:C.grad_norm_parts(e - s)]
+                C.grad_sumsq(g, part)
+                kw = dict(clip_part=part, max_norm=self.max_grad_norm if self.max_grad_norm is not None else float("inf"),
+                          skip_nonfinite=self.skip_nonfinite)
+            if self._lamb:
+                lp = self._lamb_plan_for(C, arena, s, e)
+                lamb = C.LambStep(desc=lp["desc"], meta=lp["meta"], part=lp["part"], ratios=self._trust,
+                                  exclude=group["exclude_bias_and_norm"])
+                # pass 1: the new m, v and {sum w^2, sum r^2} of every (parameter, chunk)
+                C.lamb_moments(w, g, m, v, b1, b2, eps, wd, maxim, self._adam_state, lamb, **kw)
+                kw["lamb"] = lamb
+            if self._clip_fused:
+                kw["stats"] = self._clip_stats
+            if self._ema_decay is not None:
+                kw.update(ema=arena.ema_buffer()[s:e], ema_coef=self._ema_coef)
+            kw.update(self._sched_kw(self._sched_take_advance()))
+            C.adam_step(w, g, m, v, lr_t, lr, b1, b2, eps, wd, maxim, self._adam_state, last, ctr, **kw)
+            self._adam_advanced = self._adam_advanced or last
+            return
+        if self._clip_fused or self._lamb:
+            raise RuntimeError("the step was planned into a flat launch that did not run")
+        # general path: one launch per parameter (non-arena / partial groups)
+        for k, p in enumerate(params):
+            st = self._state_of(p)
+            fin = k == len(params) - 1
+            sched = self._sched_kw(fin and self._sched_take_advance())
+            eb = st["ema_buffer"] if self._ema_decay is not None else None
+            if arena is not None and getattr(p, "_cdp_arena", None) is arena:
+                # the parameter's floats in the flat storages (its views share one layout)
+                arena.ensure_grads_in_arena([p])
+                o, n = arena.offsets[p._cdp_index], arena.numels[p._cdp_index]
+                ema = dict(ema=arena.ema_buffer()[o:o + n], ema_coef=self._ema_coef) if eb is not None else {}
+                C.adam_step(arena.data[o:o + n], arena.grad[o:o + n], arena.momentum_buffer()[o:o + n],
+                            arena.second_buffer()[o:o + n], lr_t, lr, b1, b2, eps, wd, maxim, self._adam_state,
+                            last and fin, **ema, **sched)
+                continue
+            # any other tensor: through flat contiguous copies where it is strided
+            ts = [p.data, p.grad, st["exp_avg"], st["exp_avg_sq"]] + ([eb] if eb is not None else [])
+            cs = [t.contiguous() for t in ts]
+            ema = dict(ema=cs[4].view(-1), ema_coef=self._ema_coef) if eb is not None else {}
+            C.adam_step(cs[0].view(-1), cs[1].view(-1), cs[2].view(-1), cs[3].view(-1), lr_t, lr, b1, b2, eps, wd, maxim,
+                        self._adam_state, last and fin, **ema, **sched)
+            for t, c in zip(ts, cs):
+                if c is not t and t is not p.grad:
+                    t.copy_(c)
+        self._adam_advanced = self._adam_advanced or last
+
+    _lamb_plan = None  # (key, plan) of LAMB's two passes, per arena layout
+
+    def _lamb_plan_for(self, C, arena, s, e):
+        """The (parameter, chunk) work list of LAMB's two passes over [s, e): ``lars_plan``'s, built once per
+        arena layout, outside any capture."""
+        key = (arena.layout_gen, s, e)
+        if self._lamb_plan is not None and self._lamb_plan[0] == key:
+            return self._lamb_plan[1]
+        idx = [i for i, off in enumerate(arena.offsets) if s <= off < e]
+        ps = [arena.params[i] for i in idx]
+        r = C.lars_plan(arena.data, s, e, [arena.offsets[i] for i in idx], [arena.numels[i] for i in idx],
+                        [p.dim() for p in ps], [self._slot[id(p)] for p in ps], None, None)
+        lp = {"desc": r[0], "meta": r[1], "part": r[2]}
+        self._lamb_plan = (key, lp)
+        return lp
+
+    def _step_reference(self, group, params):
+        (b1, b2), eps, wd, maxim = group["betas"], group["eps"], group["weight_decay"], group["maximize"]
+        lr = self._lr_of(group)
+        T = self._adam_t_host() + 1
+        bc1, bc2s = 1.0 - b1 ** T, math.sqrt(1.0 - b2 ** T)
+        for p in params:
+            st = self._state_of(p)
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            g = -p.grad if maxim else p.grad
+            m.mul_(b1).add_(g, alpha=1.0 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+            r = (m / bc1) / (v.sqrt() / bc2s).add_(eps)
+            adapted = self._lamb and (p.dim() > 1 or not group["exclude_bias_and_norm"])
+            if wd != 0 and (adapted or not self._lamb):
+                r = r.add(p, alpha=wd)
+            if self._lamb:
+                k = self._slot[id(p)]
+                if adapted:
+                    wn = p.detach().double().square().sum().sqrt()
+                    rn = r.double().square().sum().sqrt()
+                    q = torch.where((wn == 0) | (rn == 0), torch.ones_like(wn), wn / rn).to(p.dtype)
+                    self._trust[k].copy_(q)
+                    r = r * q
+                else:
+                    self._trust[k].fill_(1.0)
+            p.add_(r, alpha=-lr)
+            if self._ema_decay is not None:
+                self._ema_apply_reference(p)
+        self._adam_ref = True
+
+
+class LAMB(AdamW):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning"): :class:`AdamW`'s moments with a
+    layer-wise trust ratio over the Adam update. Per adapted parameter tensor
+
+        ``r = m^ / (sqrt(v^) + eps) + wd w``, ``q = |w| / |r|`` (1 when ``|w|`` or ``|r|`` is 0), ``w -= lr q r``
+
+    with the norms from fp64 sums of squares and ``q`` evaluated in fp64 and rounded once. There is NO clamp on
+    ``q`` (neither the paper's optional ``phi`` nor the ``[0, 10]`` clip of some implementations). A parameter
+    is adapted and decayed when ``w.ndim > 1`` or ``exclude_bias_and_norm`` (a ``param_groups`` entry) is
+    false; with the default exclusion biases and BatchNorm weights get ``q = 1`` and no weight decay --
+    :class:`LARS`'s rule, so the model stays one param group and one flat step. ``trust_ratios`` holds every
+    parameter's ``q``. The defaults (``lr`` 1e-3, ``betas`` (0.9, 0.999), ``eps`` 1e-6, ``weight_decay`` 0.01) are
+    the conventional ones of common implementations; nothing was measured to choose them.
+
+    MI355X path, where the step is one flat range of the arena (the conditions of the fused clip): two launches
+    over LARS's (parameter, chunk) work list. Pass 1 stores the new ``m``, ``v`` and each chunk's fp64 pair
+    ``{sum w^2, sum r^2}``; pass 2 recomputes ``r`` from the new ``m``, ``v`` with the same function (the same
+    bits: there is no arena for the update), derives its parameter's ``q`` from the pairs in its prologue and
+    applies the update and the EMA: 40 bytes per element (48 with the EMA), no host sync, no atomics on data,
+    so a captured hipGraph step adapts with each replay's own norms. Every other case evaluates the same
+    formulas per parameter with torch ops. Everything else is :class:`AdamW`'s."""
+
+    _lamb = True
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 0.01, *,
+                 exclude_bias_and_norm: bool = True, amsgrad: bool = False, maximize: bool = False, flat: bool = True,
+                 max_grad_norm: float | None = None, skip_nonfinite: bool = False, ema_decay: float | None = None,
+                 lr_schedule: LRSchedule | None = None):
+        self._extra_defaults = dict(exclude_bias_and_norm=bool(exclude_bias_and_norm))
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad=amsgrad, maximize=maximize, flat=flat,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
+                         lr_schedule=lr_schedule)
+        all_params = [p for g in self.param_groups for p in g["params"]]
+        self._slot = {id(p): k for k, p in enumerate(all_params)}
+        # allocated here, never inside a capture
+        self._trust = torch.ones(len(all_params), dtype=torch.float32, device=all_params[0].device)
+
+    @property
+    def trust_ratios(self) -> torch.Tensor:
+        """``q`` of every parameter at the last step, in ``param_groups`` order (1.0 for excluded
+        parameters): a device tensor the step writes; reading it here never syncs."""
+        return self._trust
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if hasattr(self, "_trust"):  # not the constructor's own calls
+            all_params = [p for g in self.param_groups for p in g["params"]]
+            self._slot = {id(p): k for k, p in enumerate(all_params)}
+            t = torch.ones(len(all_params), dtype=torch.float32, device=self._trust.device)
+            t[:self._trust.numel()] = self._trust
+            self._trust = t
 
 
 def _check_ema_decay(decay):

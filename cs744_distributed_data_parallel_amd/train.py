@@ -30,7 +30,7 @@ from . import distributed as dist
 from .data import MIX_MODES, DeviceLoader, DistributedSampler, MixTarget, cifar10_binary, synthetic_cifar10, synthetic_imagenet
 from .models import get_model
 from .ops import CrossEntropyLoss, count_correct
-from .optim import LARS, SGD, LRSchedule
+from .optim import LAMB, LARS, SGD, AdamW, LRSchedule
 from .parallel import (
     BucketedOverlap,
     DistributedDataParallel,
@@ -210,12 +210,22 @@ def run(rank, size, epochs, batch_size, args):
     elif strategy == "bucketed_overlap":
         sync = BucketedOverlap(model, bucket_cap_mb=args.bucket_cap_mb)
     lr_schedule = _lr_schedule_from(args, epochs, len(train_loader))
-    if args.optimizer == "lars":
-        optimizer = LARS(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
+    # --weight-decay: the reference's 1e-4 for sgd / lars, the conventional 0.01 for adamw / lamb
+    wd = args.weight_decay
+    if wd is None:
+        wd = 0.01 if args.optimizer in ("adamw", "lamb") else 0.0001
+    common = dict(max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay,
+                  lr_schedule=lr_schedule)
+    if args.optimizer in ("adamw", "lamb"):
+        cls = AdamW if args.optimizer == "adamw" else LAMB
+        kw = {} if args.adam_eps is None else {"eps": args.adam_eps}  # else the class's own default
+        optimizer = cls(model.parameters(), lr=args.lr, betas=tuple(args.betas), weight_decay=wd, **kw, **common)
+    elif args.optimizer == "lars":
+        optimizer = LARS(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=wd,
                          trust_coefficient=args.trust_coefficient, max_grad_norm=args.clip_grad_norm,
                          skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay, lr_schedule=lr_schedule)
     else:
-        optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=0.0001,
+        optimizer = SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=wd,
                         max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite,
                         ema_decay=args.ema_decay, lr_schedule=lr_schedule)
 
@@ -357,8 +367,15 @@ def parse_args(argv=None):
     p.add_argument("--lr-milestones", type=int, nargs="+", default=[], metavar="E",
                    help="epochs at which --lr-schedule step multiplies the rate by --lr-gamma")
     p.add_argument("--lr-gamma", type=float, default=0.1, metavar="G", help="factor of --lr-schedule step")
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
-                   help="sgd (the reference's) or lars: SGD with layer-wise adaptive rate scaling, for large batches")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars", "adamw", "lamb"],
+                   help="sgd (the reference's), lars: SGD with layer-wise adaptive rate scaling, for large batches, "
+                        "adamw, or lamb: AdamW's update with a layer-wise trust ratio (set --lr to suit: 1e-3 is usual)")
+    p.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.999), metavar=("B1", "B2"),
+                   help="decay rates of the two moments (--optimizer adamw / lamb)")
+    p.add_argument("--adam-eps", type=float, default=None, metavar="FLOAT",
+                   help="eps of --optimizer adamw (default 1e-8) / lamb (default 1e-6)")
+    p.add_argument("--weight-decay", type=float, default=None, metavar="FLOAT",
+                   help="weight decay (default: 1e-4 for sgd / lars, 0.01 for adamw / lamb)")
     p.add_argument("--trust-coefficient", type=float, default=0.001, metavar="FLOAT",
                    help="LARS trust coefficient (--optimizer lars)")
     p.add_argument("--clip-grad-norm", type=float, default=None, metavar="FLOAT",

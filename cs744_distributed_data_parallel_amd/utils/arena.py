@@ -91,6 +91,7 @@ class FlatArena:
         self.grad = None
         self.momentum = None
         self.ema = None  # the optimizer's weight EMA (SGD(ema_decay=...)), laid out like data
+        self.second = None  # Adam's second moment (AdamW / LAMB exp_avg_sq), laid out like data; the first is momentum
         self.claimed = [False] * len(params)
         # next-step weight preparation by the optimizer (see prep_lookup / prep_plan_for)
         self.layout_gen = 0
@@ -173,6 +174,17 @@ class FlatArena:
 
     def momentum_views(self) -> List[torch.Tensor]:
         buf = self.momentum_buffer()
+        return [_view_like(buf, off, p.data) for p, off in zip(self.params, self.offsets)]
+
+    def second_buffer(self) -> torch.Tensor:
+        """The second-moment storage of the Adam family (``exp_avg_sq``; ``exp_avg`` lives in the momentum
+        storage), zero-initialised. Nothing is allocated until an AdamW / LAMB step asks for it."""
+        if self.second is None:
+            self.second = torch.zeros(self.total, device=self.device, dtype=self.dtype)
+        return self.second
+
+    def second_views(self) -> List[torch.Tensor]:
+        buf = self.second_buffer()
         return [_view_like(buf, off, p.data) for p, off in zip(self.params, self.offsets)]
 
     def ema_buffer(self) -> torch.Tensor:
@@ -349,14 +361,15 @@ class FlatArena:
         """Permute the arena into ``new_order`` (indices into the current parameter list).
 
         Used after the first iteration to lay gradients out in their observed ready order, so every
-        bucket is a contiguous range. Parameter values, gradients, momentum and the weight EMA move
-        with their parameters; all views are re-pointed.
+        bucket is a contiguous range. Parameter values, gradients, momentum, Adam's second moment and the
+        weight EMA move with their parameters; all views are re-pointed.
         """
         new_order = list(new_order)
         if sorted(new_order) != list(range(len(self.params))):
             raise ValueError("relayout order must be a permutation of the parameter indices")
         old_params, old_offsets = self.params, self.offsets
         old_data, old_grad, old_mom, old_ema = self.data, self.grad, self.momentum, self.ema
+        old_second = self.second
         params = [old_params[i] for i in new_order]
         self._layout(params)
         self.params = params
@@ -364,6 +377,7 @@ class FlatArena:
         self.grad = None if old_grad is None else torch.zeros_like(self.data)
         self.momentum = None if old_mom is None else torch.zeros_like(self.data)
         self.ema = None if old_ema is None else torch.zeros_like(self.data)
+        self.second = None if old_second is None else torch.zeros_like(self.data)
         for new_i, old_i in enumerate(new_order):
             p = params[new_i]
             o_off, n_off = old_offsets[old_i], self.offsets[new_i]
@@ -376,6 +390,8 @@ class FlatArena:
                 _view_like(self.momentum, n_off, p.data).copy_(_view_like(old_mom, o_off, p.data))
             if old_ema is not None:
                 _view_like(self.ema, n_off, p.data).copy_(_view_like(old_ema, o_off, p.data))
+            if old_second is not None:
+                _view_like(self.second, n_off, p.data).copy_(_view_like(old_second, o_off, p.data))
             p._cdp_index = new_i
         self.claimed = [False] * len(params)
         self.layout_gen += 1  # offsets moved: any fused-step plan / products are stale

@@ -190,7 +190,7 @@ struct EmaArgs {
 // configuration, and every workgroup steps at lr_t = float32(double(base) * f(t)) with base the rate it
 // would use otherwise; workgroup 0 writes lr_t to last_lr (optional). advance != 0 (the last launch of a
 // step()): the launch also stores t + 1, by an arrival count over its workgroups (sched_arrive,
-// misc.hip); advance == 0: the launch only reads t.
+// step_common.h); advance == 0: the launch only reads t.
 struct SchedArgs {
   long long* state = nullptr;
   const LrSchedCfg* cfg = nullptr;

@@ -9,7 +9,7 @@
 // replayed hipGraph steps at a new rate every time. The configuration lives in device memory (as the
 // EMA's coefficients do), so it can be refilled between replays without re-capture.
 //
-// How t advances (SchedArgs::state = {t, arrivals}) is described at sched_arrive in misc.hip.
+// How t advances (SchedArgs::state = {t, arrivals}) is described at sched_arrive in step_common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

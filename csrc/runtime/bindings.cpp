@@ -123,6 +123,28 @@ PYBIND11_MODULE(_C, m) {
         py::arg("lars") = LarsStep{}, py::arg("ema") = py::none(), py::arg("ema_coef") = py::none(),
         py::arg("sched_state") = py::none(), py::arg("sched_cfg") = py::none(), py::arg("sched_last") = py::none(),
         py::arg("sched_advance") = false);
+  py::class_<LambStep>(m, "LambStep", "the LAMB block of adam_step / lamb_moments (default: off, AdamW)")
+      .def(py::init([](c10::optional<at::Tensor> desc, c10::optional<at::Tensor> meta, c10::optional<at::Tensor> part,
+                       c10::optional<at::Tensor> ratios, bool exclude) {
+             LambStep l;
+             l.desc = desc, l.meta = meta, l.part = part, l.ratios = ratios, l.exclude = exclude;
+             return l;
+           }),
+           py::arg("desc") = py::none(), py::arg("meta") = py::none(), py::arg("part") = py::none(),
+           py::arg("ratios") = py::none(), py::arg("exclude") = true);
+  m.def("adam_step", &adam_step, py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr_t"), py::arg("lr"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("maximize"), py::arg("state"),
+        py::arg("advance"), py::arg("counter") = py::none(), py::arg("clip_part") = py::none(),
+        py::arg("max_norm") = 0.0, py::arg("stats") = py::none(), py::arg("skip_nonfinite") = false,
+        py::arg("lamb") = LambStep{}, py::arg("ema") = py::none(), py::arg("ema_coef") = py::none(),
+        py::arg("sched_state") = py::none(), py::arg("sched_cfg") = py::none(), py::arg("sched_last") = py::none(),
+        py::arg("sched_advance") = false,
+        "AdamW (or, with a LAMB block, LAMB's pass 2) over a flat range; state = {t, arrivals} on the device");
+  m.def("lamb_moments", &lamb_moments, py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("maximize"), py::arg("state"), py::arg("lamb"),
+        py::arg("clip_part") = py::none(), py::arg("max_norm") = 0.0, py::arg("skip_nonfinite") = false,
+        "LAMB pass 1: the new exp_avg / exp_avg_sq and the fp64 pairs {sum w^2, sum r^2} of every work item");
+  m.def("adam_grid", &adam_grid_, py::arg("n"), "workgroups of the flat adam_step launch over n floats");
   m.def("lr_sched_pack", &lr_sched_pack, py::arg("kind"), py::arg("warmup_steps"), py::arg("warmup_start_factor"),
         py::arg("total_steps"), py::arg("end_factor"), py::arg("power"), py::arg("milestones"), py::arg("gamma"),
         "the learning-rate schedule's configuration as CPU bytes (kind: 0 constant, 1 cosine, 2 poly, 3 step)");

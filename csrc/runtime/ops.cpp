@@ -26,6 +26,7 @@
 #include <string>
 #include <unordered_map>
 
+#include "../kernels/adam.h"
 #include "../kernels/kernels.h"
 
 namespace cdp {
@@ -2272,6 +2273,79 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
   sgd_launch(p.data_ptr<float>(), g.data_ptr<float>(), bp, p.numel(), fptr(lr_t), (float)lr, (float)momentum,
              (float)dampening, (float)wd, (float)grad_scale, nesterov, first, maximize, cur_stream(),
              counter_ptr(counter), clip, la, ea, sa);
+}
+
+// ---------------------------------------------------------------- AdamW / LAMB over a flat arena
+namespace {
+AdamArgs adam_args(const at::Tensor& state, double beta1, double beta2, double eps, double wd, bool maximize,
+                   bool advance, const at::Tensor& like) {
+  TORCH_CHECK(state.is_cuda() && state.device() == like.device() && state.scalar_type() == at::kLong &&
+                  state.is_contiguous() && state.numel() >= 2,
+              "adam: state must be a contiguous int64 device tensor {t, arrivals}");
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam: betas in [0, 1)");
+  TORCH_CHECK(eps >= 0.0 && wd >= 0.0, "adam: eps and weight decay must not be negative");
+  AdamArgs a;
+  a.state = reinterpret_cast<long long*>(state.data_ptr<int64_t>());
+  a.beta1 = beta1, a.beta2 = beta2;
+  a.b1 = (float)beta1, a.omb1 = (float)(1.0 - beta1);
+  a.b2 = (float)beta2, a.omb2 = (float)(1.0 - beta2);
+  a.eps = (float)eps, a.wd = (float)wd;
+  a.maximize = maximize ? 1 : 0;
+  a.advance = advance ? 1 : 0;
+  return a;
+}
+void check_adam_flat(const at::Tensor& w, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v) {
+  check_flat_grad(w, "adam weights");
+  check_flat_grad(g, "adam gradients");
+  check_flat_grad(m, "adam exp_avg");
+  check_flat_grad(v, "adam exp_avg_sq");
+  TORCH_CHECK(w.numel() >= 1 && g.numel() == w.numel() && m.numel() == w.numel() && v.numel() == w.numel() &&
+                  g.device() == w.device() && m.device() == w.device() && v.device() == w.device(),
+              "adam: w, g, exp_avg and exp_avg_sq must be of one size and device");
+  TORCH_CHECK(m.data_ptr() != w.data_ptr() && v.data_ptr() != w.data_ptr() && m.data_ptr() != v.data_ptr(),
+              "adam: w, exp_avg and exp_avg_sq must be distinct storages");
+}
+LarsArgs lamb_args(const LambStep& lb, const at::Tensor& like) {
+  LarsStep ls;
+  ls.desc = lb.desc, ls.meta = lb.meta, ls.part = lb.part, ls.ratios = lb.ratios;
+  ls.exclude = lb.exclude;
+  return lars_args(ls, like, -1);
+}
+}  // namespace
+
+void adam_step(at::Tensor w, const at::Tensor& g, at::Tensor m, at::Tensor v, const c10::optional<at::Tensor>& lr_t,
+               double lr, double beta1, double beta2, double eps, double wd, bool maximize, at::Tensor state,
+               bool advance, const c10::optional<at::Tensor>& counter, const c10::optional<at::Tensor>& clip_part,
+               double max_norm, const c10::optional<at::Tensor>& stats, bool skip_nonfinite, const LambStep& lamb,
+               const c10::optional<at::Tensor>& ema, const c10::optional<at::Tensor>& ema_coef,
+               const c10::optional<at::Tensor>& sched_state, const c10::optional<at::Tensor>& sched_cfg,
+               const c10::optional<at::Tensor>& sched_last, bool sched_advance) {
+  check_adam_flat(w, g, m, v);
+  const ClipArgs clip = clip_args(clip_part, max_norm, stats, skip_nonfinite, w);
+  const EmaArgs ea = ema_args(ema, ema_coef, w);
+  const SchedArgs sa = sched_args(sched_state, sched_cfg, sched_last, sched_advance, w.device());
+  const AdamArgs ad = adam_args(state, beta1, beta2, eps, wd, maximize, advance, w);
+  const LarsArgs la = lamb_args(lamb, w);
+  adam_launch(w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), w.numel(), fptr(lr_t),
+              (float)lr, ad, cur_stream(), counter_ptr(counter), clip, la, ea, sa);
+}
+
+void lamb_moments(const at::Tensor& w, const at::Tensor& g, at::Tensor m, at::Tensor v, double beta1, double beta2,
+                  double eps, double wd, bool maximize, const at::Tensor& state, const LambStep& lamb,
+                  const c10::optional<at::Tensor>& clip_part, double max_norm, bool skip_nonfinite) {
+  check_adam_flat(w, g, m, v);
+  // the statistics of the clip are written once, by the step that follows
+  const ClipArgs clip = clip_args(clip_part, max_norm, c10::nullopt, skip_nonfinite, w);
+  const AdamArgs ad = adam_args(state, beta1, beta2, eps, wd, maximize, false, w);
+  const LarsArgs la = lamb_args(lamb, w);
+  TORCH_CHECK(la.params != nullptr, "lamb_moments: the plan of lars_plan is required");
+  lamb_moments_launch(w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), ad, clip, la,
+                      cur_stream());
+}
+
+int64_t adam_grid_(int64_t n) {
+  TORCH_CHECK(n >= 0, "adam_grid: negative size");
+  return adam_grid(n);
 }
 
 // ---------------------------------------------------------------- SGD + next-step weight preparation

@@ -130,6 +130,32 @@ void sgd_step(at::Tensor p, const at::Tensor& g, c10::optional<at::Tensor> buf, 
               const c10::optional<at::Tensor>& sched_state = c10::nullopt,
               const c10::optional<at::Tensor>& sched_cfg = c10::nullopt,
               const c10::optional<at::Tensor>& sched_last = c10::nullopt, bool sched_advance = false);
+// AdamW / LAMB over a flat range (csrc/kernels/adam.h). The LAMB block: descriptor, meta and partials from
+// lars_plan, the partials filled by lamb_moments just before; ratios: one float per parameter. Without a
+// descriptor the step is AdamW.
+struct LambStep {
+  c10::optional<at::Tensor> desc, meta, part, ratios;
+  bool exclude = true;
+};
+// One step over w, g, m (exp_avg), v (exp_avg_sq), flat and of one size. state = {t, arrivals} (int64,
+// device): every workgroup reads t; with advance (the last launch of a step()) the launch stores t + 1.
+// The clip, EMA and schedule blocks are sgd_step's.
+void adam_step(at::Tensor w, const at::Tensor& g, at::Tensor m, at::Tensor v, const c10::optional<at::Tensor>& lr_t,
+               double lr, double beta1, double beta2, double eps, double wd, bool maximize, at::Tensor state,
+               bool advance, const c10::optional<at::Tensor>& counter = c10::nullopt,
+               const c10::optional<at::Tensor>& clip_part = c10::nullopt, double max_norm = 0.0,
+               const c10::optional<at::Tensor>& stats = c10::nullopt, bool skip_nonfinite = false,
+               const LambStep& lamb = LambStep{}, const c10::optional<at::Tensor>& ema = c10::nullopt,
+               const c10::optional<at::Tensor>& ema_coef = c10::nullopt,
+               const c10::optional<at::Tensor>& sched_state = c10::nullopt,
+               const c10::optional<at::Tensor>& sched_cfg = c10::nullopt,
+               const c10::optional<at::Tensor>& sched_last = c10::nullopt, bool sched_advance = false);
+// LAMB pass 1: the new m, v and the fp64 pairs {sum w^2, sum r^2} of lamb's work list (reads t only)
+void lamb_moments(const at::Tensor& w, const at::Tensor& g, at::Tensor m, at::Tensor v, double beta1, double beta2,
+                  double eps, double wd, bool maximize, const at::Tensor& state, const LambStep& lamb,
+                  const c10::optional<at::Tensor>& clip_part = c10::nullopt, double max_norm = 0.0,
+                  bool skip_nonfinite = false);
+int64_t adam_grid_(int64_t n);  // workgroups of the flat adam_step launch over n floats (without LAMB)
 // Learning-rate schedule of the fused step (csrc/kernels/lr_sched.h). sched_state = {t, arrivals} (int64,
 // device), sched_cfg = lr_sched_pack's bytes moved to the device, sched_last = one float32 that receives the
 // rate of the launch (optional); sched_advance: this launch is the last of its step() and stores t + 1.
