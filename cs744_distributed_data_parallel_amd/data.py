@@ -162,6 +162,7 @@ class MixTarget(NamedTuple):
 
 
 MIX_MODES = ("none", "mixup", "cutmix")
+ERASE_MODES = ("const", "rand", "pixel")
 
 
 class DeviceLoader:
@@ -189,12 +190,28 @@ class DeviceLoader:
     before the normalisation. Each batch's windows are kept in ``last_crops`` (int32 ``[B, 5]``:
     ``top, left, h, w, flip``); mixup / CutMix compose (the CutMix box is in output pixels). With all four
     arguments at their defaults the loader is exactly what it is without them, and ``last_crops`` is None.
+
+    ``erase_prob`` > 0 (and ``train=True``) turns on RandomErasing (Zhong et al.) in the same kernel: with
+    that probability an image loses one box of ``U(erase_scale)`` of the output area and an aspect ratio
+    ``h / w`` log-uniform in ``erase_ratio`` (torchvision's ``RandomErasing.get_params`` rule, drawn on the
+    device from the step counter; a proposal needs ``1 <= h < H`` and ``1 <= w < W``, and after 10 rejected
+    proposals the image is left alone). The box is in output pixels, on the normalised tensor, after crop,
+    resize and flip and **before** the mix: the partner of a mixed image shows its own box. ``erase_mode``:
+    ``"const"`` fills with ``erase_value`` (a float or three, in normalised units; 0 is torchvision's
+    ``value=0`` after ``Normalize``), ``"rand"`` with one N(0, 1) value per channel per image (timm's
+    ``rand``), ``"pixel"`` with one per element (torchvision's ``value="random"``, timm's ``pixel``). Each
+    batch's boxes are kept in ``last_erase`` (int32 ``[B, 5]``: ``on, top, left, h, w``; all 0 for an image
+    that was not erased); ``erase_schedule`` and ``erase_noise`` give the boxes and the noise of any step.
+    ``train=False`` ignores the erase arguments. With ``erase_prob=0`` the loader is exactly what it is
+    without them, and ``last_erase`` is None.
     """
 
     def __init__(self, dataset: ImageDataset, batch_size: int, sampler=None, shuffle: bool = False,
                  train: bool = True, drop_last: bool = False, seed: int = 0, mixup_alpha: float = 0.0,
                  cutmix_alpha: float = 0.0, mix_prob: float = 1.0, mix_switch_prob: float = 0.5,
-                 out_size=None, rrc_scale=None, rrc_ratio=(3.0 / 4.0, 4.0 / 3.0), center_crop=None):
+                 out_size=None, rrc_scale=None, rrc_ratio=(3.0 / 4.0, 4.0 / 3.0), center_crop=None,
+                 erase_prob: float = 0.0, erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3),
+                 erase_mode: str = "const", erase_value=0.0):
         if not (mixup_alpha >= 0.0 and cutmix_alpha >= 0.0):
             raise ValueError(f"mixup_alpha and cutmix_alpha must be >= 0. Got: {mixup_alpha}, {cutmix_alpha}")
         if not (0.0 <= mix_prob <= 1.0 and 0.0 <= mix_switch_prob <= 1.0):
@@ -223,6 +240,22 @@ class DeviceLoader:
         self.resizing = rrc_scale is not None if train else (out_size is not None or center_crop is not None)
         self.out_size = out_size if out_size is not None else tuple(dataset.images.shape[1:3])
         self.last_crops = None
+        if not (0.0 <= float(erase_prob) <= 1.0):
+            raise ValueError(f"erase_prob must be in [0, 1]. Got: {erase_prob}")
+        erase_scale = tuple(float(v) for v in erase_scale)
+        if not (len(erase_scale) == 2 and 0.0 < erase_scale[0] <= erase_scale[1] <= 1.0):
+            raise ValueError(f"erase_scale must be (lo, hi) with 0 < lo <= hi <= 1. Got: {erase_scale}")
+        erase_ratio = tuple(float(v) for v in erase_ratio)
+        if not (len(erase_ratio) == 2 and 0.0 < erase_ratio[0] <= erase_ratio[1] < math.inf):
+            raise ValueError(f"erase_ratio must be (lo, hi) with 0 < lo <= hi. Got: {erase_ratio}")
+        if erase_mode not in ERASE_MODES:
+            raise ValueError(f"erase_mode must be one of {ERASE_MODES}. Got: {erase_mode!r}")
+        value = [float(erase_value)] * 3 if isinstance(erase_value, (int, float)) else [float(v) for v in erase_value]
+        if not (len(value) == 3 and all(math.isfinite(v) for v in value)):
+            raise ValueError(f"erase_value must be a finite float or three of them. Got: {erase_value}")
+        self.erase_prob, self.erase_scale, self.erase_ratio = float(erase_prob), erase_scale, erase_ratio
+        self.erase_mode, self.erase_value = erase_mode, value
+        self.last_erase = None
         self.ds, self.batch_size, self.sampler, self.shuffle = dataset, batch_size, sampler, shuffle
         self.train, self.drop_last, self.seed = train, drop_last, seed
         self.dev = dataset.images.device
@@ -291,6 +324,11 @@ class DeviceLoader:
         """Whether batches are mixed (an alpha > 0 on a training loader) and carry a :class:`MixTarget`."""
         return self.train and (self.mixup_alpha > 0.0 or self.cutmix_alpha > 0.0)
 
+    @property
+    def erasing(self) -> bool:
+        """Whether images are erased (``erase_prob`` > 0 on a training loader)."""
+        return self.train and self.erase_prob > 0.0
+
     def batch(self, idx: torch.Tensor, offset: int, bsz: int, out: Optional[torch.Tensor] = None,
               nbatches: int = 0):
         """Produce one batch from ``idx[offset:offset+bsz]`` (graph-capturable on GPU).
@@ -307,6 +345,12 @@ class DeviceLoader:
         if self.dev.type == "cuda":
             C = _native.lib()
             target = torch.empty(bsz, dtype=torch.int64, device=self.dev)
+            ekw = {}
+            if self.erasing:
+                # the same launch draws every image's box from the step counter, fills it and publishes it
+                self.last_erase = torch.empty(bsz, 5, dtype=torch.int32, device=self.dev)
+                ekw = dict(erase_prob=self.erase_prob, erase_scale=self.erase_scale, erase_ratio=self.erase_ratio,
+                           erase_mode=self.erase_mode, erase_value=self.erase_value, erase=self.last_erase)
             if self.resizing:
                 OH, OW = self.out_size
                 if out is not None and tuple(out.shape) != (bsz, self.ds.shape[2], OH, OW):
@@ -321,10 +365,10 @@ class DeviceLoader:
                     info = torch.empty(8, dtype=torch.float32, device=self.dev)
                     data = C.augment_resize(*args, mixup_alpha=self.mixup_alpha, cutmix_alpha=self.cutmix_alpha,
                                             mix_prob=self.mix_prob, mix_switch_prob=self.mix_switch_prob, mix=info,
-                                            labels_b=target_b)
+                                            labels_b=target_b, **ekw)
                     target = MixTarget(target, target_b, info[1:2], info)
                 else:
-                    data = C.augment_resize(*args)
+                    data = C.augment_resize(*args, **ekw)
                 self.last_crops = crops
             elif self.mixing:
                 # the same launch draws the batch's mix from the step counter, applies it and publishes it
@@ -333,28 +377,32 @@ class DeviceLoader:
                 data = C.augment(self.ds.images, idx, offset, bsz, self.ds.mean, self.ds.std, pad, flip, self._counter,
                                  self.seed, out, nbatches, self.ds.labels, target, mixup_alpha=self.mixup_alpha,
                                  cutmix_alpha=self.cutmix_alpha, mix_prob=self.mix_prob,
-                                 mix_switch_prob=self.mix_switch_prob, mix=info, labels_b=target_b)
+                                 mix_switch_prob=self.mix_switch_prob, mix=info, labels_b=target_b, **ekw)
                 target = MixTarget(target, target_b, info[1:2], info)
             else:
                 data = C.augment(self.ds.images, idx, offset, bsz, self.ds.mean, self.ds.std, pad, flip,
-                                 self._counter, self.seed, out, nbatches, self.ds.labels, target)
+                                 self._counter, self.seed, out, nbatches, self.ds.labels, target, **ekw)
             if not self._external_advance:
                 C.counter_inc(self._counter)
             else:
                 self._check_one_batch_per_step()
             return data, target
-        ctr = int(self._counter.item()) if (nbatches > 0 or self.mixing or self.resizing) else None
+        ctr = int(self._counter.item()) if (nbatches > 0 or self.mixing or self.resizing or self.erasing) else None
         if nbatches > 0:
             offset += (ctr % nbatches) * bsz
         if self.resizing:
             self._counter += 1
             data, target = self._cpu_resize_batch(idx[offset : offset + bsz], flip, ctr)
+            if self.erasing:
+                data = self._cpu_erase(data, ctr)
             if out is not None:
                 data = out.copy_(data)
             return self._cpu_mix(data, target, ctr) if self.mixing else (data, target)
         if ctr is not None and not pad:
             self._counter += 1  # (the padded path advances it itself)
         data, target = self._cpu_batch(idx[offset : offset + bsz], pad, flip)
+        if self.erasing:
+            data = self._cpu_erase(data, ctr)
         if self.mixing:
             return self._cpu_mix(data, target, ctr)
         return data, target
@@ -374,6 +422,87 @@ class DeviceLoader:
             raise ValueError("crop_schedule: a training loader with rrc_scale draws windows; this one does not")
         H, W = self.ds.shape[:2]
         return _native.lib().rrc_params(self.seed, first_counter, n, B, self.rrc_scale, self.rrc_ratio, H, W)
+
+    def _erase_size(self):
+        return self.out_size if self.resizing else tuple(self.ds.shape[:2])
+
+    def erase_schedule(self, first_counter: int, n: int, B: int) -> torch.Tensor:
+        """The RandomErasing rows ``{on, top, left, h, w}`` of the ``B`` images of the batches at step counters
+        ``first_counter .. first_counter + n - 1`` (int32 ``[n, B, 5]``; training loaders with ``erase_prob`` > 0)."""
+        if not self.erasing:
+            raise ValueError("erase_schedule: a training loader with erase_prob > 0 draws boxes; this one does not")
+        H, W = self._erase_size()
+        if self.dev.type == "cuda":
+            return _native.lib().erase_params(self.seed, first_counter, n, B, self.erase_prob, self.erase_scale,
+                                              self.erase_ratio, H, W)
+        rows = torch.zeros(n, B, 5, dtype=torch.int32)
+        for i in range(n):
+            g = self._cpu_erase_generator(first_counter + i)
+            for b in range(B):
+                rows[i, b] = torch.tensor(self._erase_get_params(H, W, self.erase_prob, self.erase_scale,
+                                                                 self.erase_ratio, g), dtype=torch.int32)
+        return rows
+
+    def erase_noise(self, counter: int, B: int) -> torch.Tensor:
+        """The N(0, 1) fill noise of the ``B`` images of the batch at step counter ``counter`` (float32
+        ``[B, 3, H, W]`` channels_last, H x W the output size): ``"pixel"`` fills element ``(b, c, y, x)`` of a
+        box with ``[b, c, y, x]``, ``"rand"`` fills the whole box of channel ``c`` with ``[b, c, 0, 0]``."""
+        if not self.erasing:
+            raise ValueError("erase_noise: a training loader with erase_prob > 0 erases; this one does not")
+        H, W = self._erase_size()
+        if self.dev.type == "cuda":
+            return _native.lib().erase_noise(self.seed, counter, B, H, W)
+        g = torch.Generator().manual_seed((0x6E6F697365 << 24) + self.seed * 1000003 + counter)
+        return torch.randn(B, H, W, 3, generator=g).permute(0, 3, 1, 2)
+
+    def _cpu_erase_generator(self, ctr):
+        return torch.Generator().manual_seed((0x6572617365 << 24) + self.seed * 1000003 + ctr)
+
+    @staticmethod
+    def _erase_get_params(H, W, prob, scale, ratio, g):
+        """torchvision's ``RandomErasing.get_params`` rule with draws from the generator ``g``: the row
+        ``(on, top, left, h, w)`` of one image. One probability draw, then 10 proposals of four draws each (area,
+        aspect ``h / w``, top, left), all taken from ``g`` whether used or not; a proposal needs ``1 <= h < H`` and
+        ``1 <= w < W``."""
+        u = torch.rand(41, generator=g, dtype=torch.float64).tolist()
+        if not u[0] < prob:
+            return 0, 0, 0, 0, 0
+        area = H * W
+        log_lo, log_hi = math.log(ratio[0]), math.log(ratio[1])
+        for i in range(10):
+            u_s, u_r, u_t, u_l = u[1 + 4 * i : 5 + 4 * i]
+            target = area * (scale[0] + (scale[1] - scale[0]) * u_s)
+            aspect = math.exp(log_lo + (log_hi - log_lo) * u_r)
+            h, w = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+            if 1 <= h < H and 1 <= w < W:
+                return 1, min(int(u_t * (H - h + 1)), H - h), min(int(u_l * (W - w + 1)), W - w), h, w
+        return 0, 0, 0, 0, 0
+
+    def _cpu_erase(self, data, ctr):
+        """The device kernels' semantics on the host: per image the box rule from a generator of its own (seeded
+        apart from the crop / flip, window and mix generators, whose draws are therefore unchanged), the fill of
+        the mode (the noise from a second generator: ``erase_noise`` returns it for any counter), and the
+        published rows in ``last_erase``. It runs before ``_cpu_mix``, whose partner ``data.flip(0)`` then shows
+        every image's own box."""
+        B, _, H, W = data.shape
+        rows = self.erase_schedule(ctr, 1, B)[0]
+        self.last_erase = rows
+        if not bool(rows[:, 0].any()):
+            return data
+        data = data.clone(memory_format=torch.channels_last)
+        noise = self.erase_noise(ctr, B) if self.erase_mode != "const" else None
+        value = torch.tensor(self.erase_value, dtype=torch.float32).view(3, 1, 1)
+        for b, (on, top, left, h, w) in enumerate(rows.tolist()):
+            if not on:
+                continue
+            if self.erase_mode == "const":
+                fill = value
+            elif self.erase_mode == "rand":
+                fill = noise[b, :, :1, :1]
+            else:
+                fill = noise[b, :, top : top + h, left : left + w]
+            data[b, :, top : top + h, left : left + w] = fill
+        return data
 
     @staticmethod
     def _rrc_get_params(H, W, scale, ratio, g):

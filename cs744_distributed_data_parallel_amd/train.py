@@ -126,6 +126,15 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 top, left, h, w = crops[0, :4].tolist()
                 print("[cdp] rank {}: crop of image 0 in iter {} is {} x {} at ({}, {})".format(
                     rank, iter_number, h, w, top, left), file=sys.stderr)
+            erase = getattr(train_loader, "last_erase", None)
+            if erase is not None and not (data.is_cuda and torch.cuda.is_current_stream_capturing()):
+                # RandomErasing: the first image's box in the window's last batch (stderr, as above)
+                import sys
+
+                on, top, left, h, w = erase[0].tolist()
+                print("[cdp] rank {}: erase of image 0 in iter {} is {}".format(
+                    rank, iter_number, "{} x {} at ({}, {})".format(h, w, top, left) if on else "none"),
+                    file=sys.stderr)
         if max_iters is not None and iter_number >= max_iters:
             break
         iter_number += 1
@@ -185,7 +194,9 @@ def run(rank, size, epochs, batch_size, args):
                                 seed=args.seed, mixup_alpha=args.mixup_alpha, cutmix_alpha=args.cutmix_alpha,
                                 mix_prob=args.mix_prob, mix_switch_prob=args.mix_switch_prob,
                                 out_size=args.crop_size if args.rrc_scale is not None else None,
-                                rrc_scale=args.rrc_scale, rrc_ratio=args.rrc_ratio)
+                                rrc_scale=args.rrc_scale, rrc_ratio=args.rrc_ratio, erase_prob=args.random_erase,
+                                erase_scale=args.erase_scale, erase_ratio=args.erase_ratio,
+                                erase_mode=args.erase_mode)
     print("Size of training set is {}".format(len(train_loader)))
     test_set = build_data(args, device, False)
     test_loader = DeviceLoader(test_set, batch_size, shuffle=False, train=False, out_size=args.crop_size,
@@ -400,6 +411,15 @@ def parse_args(argv=None):
                         "to --crop-size (replaces the pad-shift RandomCrop)")
     p.add_argument("--rrc-ratio", type=float, nargs=2, default=(3.0 / 4.0, 4.0 / 3.0), metavar=("LO", "HI"),
                    help="aspect ratio range of the RandomResizedCrop window (log-uniform)")
+    p.add_argument("--random-erase", type=float, default=0.0, metavar="PROB",
+                   help="RandomErasing of the training images: one box per image with probability PROB, after crop / "
+                        "resize / flip / normalise and before mixup / CutMix (0: off)")
+    p.add_argument("--erase-mode", choices=("const", "rand", "pixel"), default="const",
+                   help="the erased box's fill: zeros (const), one N(0, 1) value per channel (rand) or per element (pixel)")
+    p.add_argument("--erase-scale", type=float, nargs=2, default=(0.02, 0.33), metavar=("LO", "HI"),
+                   help="the erased box's share of the image area")
+    p.add_argument("--erase-ratio", type=float, nargs=2, default=(0.3, 3.3), metavar=("LO", "HI"),
+                   help="the erased box's aspect ratio h / w (log-uniform)")
     p.add_argument("--crop-size", type=int, default=None, metavar="S",
                    help="output side of both loaders (training: with --rrc-scale; default: the stored size)")
     p.add_argument("--center-crop", type=float, default=None, metavar="FRAC",

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "erase.h"
 #include "lars.h"
 #include "lr_sched.h"
 #include "mix.h"
@@ -343,30 +344,38 @@ void clip_scale_launch(float* g, long long n, const double* part, int nparts, fl
                        hipStream_t st);
 // nbatches > 0: batch offset idx_off + (counter % nbatches) * B; labels_out[b] = labels[idx[...]] when given.
 // cfg with an alpha > 0 (mix.h): mixup / CutMix of image b with image B - 1 - b in the same launch, the
-// batch's parameters published in mix[kMixRow], labels_b[b] = the partner's label
+// batch's parameters published in mix[kMixRow], labels_b[b] = the partner's label.
+// ecfg with prob > 0 (erase.h; 3-channel images): RandomErasing of every image in the same launch, before
+// the mix, image b's row {on, top, left, h, w} published in erase[b][kEraseRow]
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,
                     unsigned long long seed, float* out, hipStream_t st, long long nbatches = 0,
                     const long long* labels = nullptr, long long* labels_out = nullptr,
                     const MixCfg& cfg = MixCfg{0.f, 0.f, 1.f, 0.5f}, float* mix = nullptr,
-                    long long* labels_b = nullptr);
+                    long long* labels_b = nullptr, const EraseCfg& ecfg = EraseCfg{}, int* erase = nullptr);
 // mix[i][kMixRow] = the row the augment kernel publishes at step counter first + i, i < n
 void mix_params_launch(unsigned long long seed, long long first, long long n, const MixCfg& cfg, int H, int W,
                        float* mix, hipStream_t st);
 // The augment launch with a resize (3-channel images): out[b] (NHWC fp32, OH x OW) is a window of image b
 // resampled bilinearly. train: the window is rrc_draw(seed, counter, b, rc, H, W) (rrc.h); otherwise the central
 // (round(center_frac H), round(center_frac W)). crops[b][kCropRow] = {top, left, h, w, flip}. idx, nbatches,
-// labels and the mix arguments are augment_launch's; the CutMix box is in output pixels.
+// labels, the mix and the erase arguments are augment_launch's; the CutMix and the erase boxes are in output pixels.
 void augment_resize_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W,
                            int C, int OH, int OW, const float* mean, const float* inv_std, bool train,
                            const RrcCfg& rc, double center_frac, bool flip, const long long* counter,
                            unsigned long long seed, float* out, hipStream_t st, long long nbatches,
                            const long long* labels, long long* labels_out, int* crops,
                            const MixCfg& cfg = MixCfg{0.f, 0.f, 1.f, 0.5f}, float* mix = nullptr,
-                           long long* labels_b = nullptr);
+                           long long* labels_b = nullptr, const EraseCfg& ecfg = EraseCfg{}, int* erase = nullptr);
 // win[i][b][4] = the window {top, left, h, w} of step counter first + i and image slot b, i < n, b < B
 void rrc_params_launch(unsigned long long seed, long long first, long long n, int B, const RrcCfg& rc, int H, int W,
                        int* win, hipStream_t st);
+// rows[i][b][kEraseRow] = the row {on, top, left, h, w} the augment kernels publish at step counter first + i for
+// image slot b of an H x W output, i < n, b < B
+void erase_params_launch(unsigned long long seed, long long first, long long n, int B, const EraseCfg& ecfg, int H,
+                         int W, int* rows, hipStream_t st);
+// out[b][y][x][c] (NHWC fp32) = erase_noise(seed, counter, b, (y W + x) 3 + c): the fill noise of one step counter
+void erase_noise_launch(unsigned long long seed, long long counter, int B, int H, int W, float* out, hipStream_t st);
 // zeros into the NHWC dX pixels of the sub-pixel parity classes set in mask (bit 2 ph + pw)
 // dst[0 .. bytes) = src[0 .. bytes) as a kernel (16-B accesses when both pointers and bytes allow)
 void copy_bytes_launch(void* dst, const void* src, long long bytes, hipStream_t st);

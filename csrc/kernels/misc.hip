@@ -15,6 +15,7 @@
 
 #include "act_max.h"
 #include "common.h"
+#include "erase.h"
 #include "grad_clip.h"
 #include "lars.h"
 #include "kernels.h"
@@ -730,7 +731,11 @@ __device__ __forceinline__ const unsigned char* aug_pixel(const AugImage& a, int
 //   cutmix  out[b] = X[p] inside the box, X[b] outside (bitwise)
 //   none    out[b] = X[b] (bitwise; the partner image is not read)
 // and labels_b[b] = labels of image p. The partner's crop and flip are its own draws (hashed with p).
-template <bool MIX>
+// ERASE (RandomErasing on, see erase.h; 3-channel images): X above is X_e, the batch with every image's
+// own box filled: X_e[b] = fill(b) inside erase_draw(b)'s box and X[b] (bitwise) outside. Erasing comes
+// before mixing, so the partner shows its own box and noise (keyed by p), exactly as in its own output.
+// Every workgroup evaluates the draws itself, workgroup (0, b) publishes image b's row in erase[b][5].
+template <bool MIX, bool ERASE>
 __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __restrict__ imgs,
                                                      const long long* __restrict__ idx, long long idx_off, int B,
                                                      int H, int W, int C, float m0, float m1, float m2, float is0,
@@ -739,7 +744,8 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
                                                      float* __restrict__ out, long long nbatches,
                                                      const long long* __restrict__ labels,
                                                      long long* __restrict__ labels_out, MixCfg cfg,
-                                                     float* __restrict__ mix, long long* __restrict__ labels_b) {
+                                                     float* __restrict__ mix, long long* __restrict__ labels_b,
+                                                     EraseCfg ecfg, int* __restrict__ erase) {
   const int b = blockIdx.y;
   if (b >= B) return;
   const unsigned long long ctr = counter ? (unsigned long long)counter[0] : 0ull;
@@ -753,10 +759,19 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
   const float istd[3] = {is0, is1, is2};
   const int npix = H * W;
   float* dst = out + (long long)b * npix * C;
+  EraseImg ea, eb;
+  if (ERASE) {
+    ea = erase_image(seed, ctr, b, ecfg, H, W);
+    if (blockIdx.x == 0 && threadIdx.x == 0) erase_publish(erase + (long long)b * kEraseRow, ea.bx);
+  }
   if (!MIX) {
     // one thread per output pixel, all its channels (one index decode per pixel, not per element)
     for (int px = blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += gridDim.x * blockDim.x) {
       const int h = px / W, w = px - (px / W) * W;
+      if (ERASE && erase_in(ea.bx, h, w)) {  // (an erased pixel does not read its source)
+        for (int c = 0; c < 3; ++c) dst[(long long)px * 3 + c] = erase_fill(ea, ecfg.mode, px, c);
+        continue;
+      }
       bool in;
       const unsigned char* sp = aug_pixel(ia, h, w, H, W, C, in);
       for (int c = 0; c < C; ++c) {
@@ -775,6 +790,7 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
     if (b == 0 && mix) mix_publish(mix, mp);
   }
   const AugImage ib = aug_image(imgs, src_p, H, W, C, pad, flip, seed, ctr, p);
+  if (ERASE && mp.mode != kMixNone) eb = erase_image(seed, ctr, p, ecfg, H, W);
   // The mode is uniform over the grid: mixup reads both images; CutMix and none read one source per
   // pixel, in the unmixed kernel's loop.
   if (mp.mode == kMixMixup) {
@@ -784,11 +800,14 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
       bool ina, inb;
       const unsigned char* spa = aug_pixel(ia, h, w, H, W, C, ina);
       const unsigned char* spb = aug_pixel(ib, h, w, H, W, C, inb);
+      const bool era = ERASE && erase_in(ea.bx, h, w), erb = ERASE && erase_in(eb.bx, h, w);
       for (int c = 0; c < C; ++c) {
         const float va = ina ? (float)spa[c] * (1.f / 255.f) : 0.f;
         const float vb = inb ? (float)spb[c] * (1.f / 255.f) : 0.f;
         const int ci = c < 3 ? c : 2;
-        const float xa = (va - mean[ci]) * istd[ci], xb = (vb - mean[ci]) * istd[ci];
+        float xa = (va - mean[ci]) * istd[ci], xb = (vb - mean[ci]) * istd[ci];
+        if (era) xa = erase_fill(ea, ecfg.mode, px, ci);
+        if (erb) xb = erase_fill(eb, ecfg.mode, px, ci);
         dst[(long long)px * C + c] = lam * xa + oml * xb;
       }
     }
@@ -799,6 +818,10 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
     const int h = px / W, w = px - (px / W) * W;
     // CutMix: the pixel comes whole from the partner inside the box, from the image itself outside
     const bool box = cut && h >= mp.y0 && h < mp.y1 && w >= mp.x0 && w < mp.x1;
+    if (ERASE && erase_in(box ? eb.bx : ea.bx, h, w)) {  // the source image's own box and noise
+      for (int c = 0; c < 3; ++c) dst[(long long)px * 3 + c] = erase_fill(box ? eb : ea, ecfg.mode, px, c);
+      continue;
+    }
     AugImage s;
     s.src = box ? ib.src : ia.src;
     s.oy = box ? ib.oy : ia.oy;
@@ -894,17 +917,23 @@ __device__ __forceinline__ float rsz_sample(const RszRows& rw, const RszTap& ct,
 // it through LDS; the per-column taps (flip included) are computed once per workgroup, also in LDS.
 // MIX: as augment_kernel's, with X the batch the <false> instantiation writes: the partner p = B - 1 - b
 // is resampled through its own window and flip, and the CutMix box is in output pixels.
-template <bool MIX>
+// ERASE: as augment_kernel's, the boxes in OH x OW output pixels. Thread 0 draws the one or two boxes with
+// the windows and shares them through the same LDS hand-off (no barrier of its own); erased values
+// replace a pixel's lanes of v[12] before the store, so the 16-byte store path is the plain one. The box
+// test is uniform over every wavefront that a box's edge does not cross.
+template <bool MIX, bool ERASE>
 __global__ __launch_bounds__(256) void augment_resize_kernel(
     const unsigned char* __restrict__ imgs, const long long* __restrict__ idx, long long idx_off, int B, int H, int W,
     int OH, int OW, float m0, float m1, float m2, float is0, float is1, float is2, int train, RrcCfg rc, int eh, int ew,
     int flip, const long long* __restrict__ counter, unsigned long long seed, float* __restrict__ out,
     long long nbatches, const long long* __restrict__ labels, long long* __restrict__ labels_out,
-    int* __restrict__ crops, MixCfg cfg, float* __restrict__ mix, long long* __restrict__ labels_b, int vec) {
+    int* __restrict__ crops, MixCfg cfg, float* __restrict__ mix, long long* __restrict__ labels_b, int vec,
+    EraseCfg ecfg, int* __restrict__ erase) {
   constexpr int NI = MIX ? 2 : 1;
   __shared__ RszWin s_win[NI];
   __shared__ MixParams s_mp;
   __shared__ RszTap s_tap[NI][kRszCols];
+  __shared__ EraseImg s_er[NI];  // (referenced under ERASE only)
   const int b = blockIdx.y;
   if (b >= B) return;
   const unsigned long long ctr = counter ? (unsigned long long)counter[0] : 0ull;
@@ -921,6 +950,11 @@ __global__ __launch_bounds__(256) void augment_resize_kernel(
       s_win[NI - 1] = rsz_window(train, rc, eh, ew, flip, seed, ctr, p, H, W);
     }
     s_mp = mp;
+    if (ERASE) {
+      s_er[0] = erase_image(seed, ctr, b, ecfg, OH, OW);
+      if (MIX && mp.mode != kMixNone) s_er[NI - 1] = erase_image(seed, ctr, p, ecfg, OH, OW);
+      if (blockIdx.x == 0) erase_publish(erase + (long long)b * kEraseRow, s_er[0].bx);
+    }
     if (blockIdx.x == 0) {
       if (labels_out) labels_out[b] = labels[src_a];
       int* row = crops + (long long)b * kCropRow;
@@ -940,6 +974,11 @@ __global__ __launch_bounds__(256) void augment_resize_kernel(
   const int mode = MIX ? s_mp.mode : kMixNone;  // uniform over the grid
   const int by0 = s_mp.y0, by1 = s_mp.y1, bx0 = s_mp.x0, bx1 = s_mp.x1;
   const float lam = s_mp.lam, oml = 1.f - s_mp.lam;
+  EraseImg ea, ep;
+  if (ERASE) {
+    ea = s_er[0];
+    ep = s_er[NI - 1];  // (drawn, and used below, only when the batch is mixed)
+  }
   const float mean[3] = {m0, m1, m2};
   const float istd[3] = {is0, is1, is2};
   const int nq = (OW + 3) >> 2;           // quads per row
@@ -968,11 +1007,17 @@ __global__ __launch_bounds__(256) void augment_resize_kernel(
         const int x = x0 + j;
         const int xl = min(x, OW - 1) - c0;  // (a lane past the row's end computes its last pixel again)
         const RszTap ta = s_tap[0][xl];
+        const long long pix = (long long)y * OW + x;  // (past the row's end: in no box, and not stored)
         if (MIX && mode == kMixMixup) {
           const RszTap tb = s_tap[NI - 1][xl];
+          const bool era = ERASE && erase_in(ea.bx, y, x), erb = ERASE && erase_in(ep.bx, y, x);
 #pragma unroll
-          for (int c = 0; c < 3; ++c)
-            v[3 * j + c] = lam * rsz_sample(ra, ta, c, mean[c], istd[c]) + oml * rsz_sample(rb, tb, c, mean[c], istd[c]);
+          for (int c = 0; c < 3; ++c) {
+            float xa = rsz_sample(ra, ta, c, mean[c], istd[c]), xb = rsz_sample(rb, tb, c, mean[c], istd[c]);
+            if (era) xa = erase_fill(ea, ecfg.mode, pix, c);
+            if (erb) xb = erase_fill(ep, ecfg.mode, pix, c);
+            v[3 * j + c] = lam * xa + oml * xb;
+          }
         } else if (MIX && mode == kMixCutmix) {
           // the pixel comes whole from the partner inside the box, from the image itself outside
           const bool box = y >= by0 && y < by1 && x >= bx0 && x < bx1;
@@ -984,9 +1029,17 @@ __global__ __launch_bounds__(256) void augment_resize_kernel(
           rs.w1 = box ? rb.w1 : ra.w1;
 #pragma unroll
           for (int c = 0; c < 3; ++c) v[3 * j + c] = rsz_sample(rs, ts, c, mean[c], istd[c]);
+          if (ERASE && erase_in(box ? ep.bx : ea.bx, y, x)) {  // the source image's own box and noise
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[3 * j + c] = erase_fill(box ? ep : ea, ecfg.mode, pix, c);
+          }
         } else {
 #pragma unroll
           for (int c = 0; c < 3; ++c) v[3 * j + c] = rsz_sample(ra, ta, c, mean[c], istd[c]);
+          if (ERASE && erase_in(ea.bx, y, x)) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[3 * j + c] = erase_fill(ea, ecfg.mode, pix, c);
+          }
         }
       }
       float* o = dst + ((long long)y * OW + x0) * 3;
@@ -1018,6 +1071,24 @@ __global__ __launch_bounds__(256) void rrc_params_kernel(unsigned long long seed
   win[4 * i + 1] = r.left;
   win[4 * i + 2] = r.h;
   win[4 * i + 3] = r.w;
+}
+
+// rows[i][b] = {on, top, left, h, w}: erase_draw of step counter first + i and image slot b, i < n (the rows a
+// loader will publish: the counterpart of rrc_params_kernel)
+__global__ __launch_bounds__(256) void erase_params_kernel(unsigned long long seed, long long first, long long total,
+                                                          int B, EraseCfg ecfg, int H, int W, int* __restrict__ rows) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  erase_publish(rows + i * kEraseRow, erase_draw(seed, (unsigned long long)(first + i / B), (int)(i % B), ecfg, H, W));
+}
+// out[b][y][x][c] = erase_noise(seed, ctr, b, (y OW + x) 3 + c): the fill noise of one counter, through the
+// function the augment kernels call (per3 = 3 OH OW elements per image)
+__global__ __launch_bounds__(256) void erase_noise_kernel(unsigned long long seed, unsigned long long ctr,
+                                                         long long total, long long per3, float* __restrict__ out) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long b = i / per3;
+    out[i] = erase_noise(seed, ctr, (int)b, i - b * per3);
+  }
 }
 
 __global__ void counter_inc_kernel(long long* c) { c[0] += 1; }
@@ -1701,11 +1772,20 @@ void sgd_prep_launch(float* p, const float* g, float* buf, const SgdPrepSeg* seg
 #undef CDP_SGD_PREP_E
 #undef CDP_SGD_PREP_S
 }
+namespace {
+bool erase_cfg_ok(const EraseCfg& e) {
+  return e.prob >= 0.f && e.prob <= 1.f && e.scale_lo > 0.f && e.scale_lo <= e.scale_hi && e.scale_hi <= 1.f &&
+         e.log_ratio_lo <= e.log_ratio_hi && e.mode >= kEraseConst && e.mode <= kErasePixel &&
+         std::isfinite(e.value[0]) && std::isfinite(e.value[1]) && std::isfinite(e.value[2]);
+}
+const char* const kEraseCfgMsg =
+    ": erase prob in [0, 1], 0 < scale_lo <= scale_hi <= 1, ratio_lo <= ratio_hi, mode const / rand / pixel, finite values";
+}  // namespace
 void augment_launch(const unsigned char* imgs, const long long* idx, long long idx_off, int B, int H, int W, int C,
                     const float* mean, const float* inv_std, int pad, bool flip, const long long* counter,
                     unsigned long long seed, float* out, hipStream_t st, long long nbatches,
                     const long long* labels, long long* labels_out, const MixCfg& cfg, float* mix,
-                    long long* labels_b) {
+                    long long* labels_b, const EraseCfg& ecfg, int* erase) {
   dim3 grid((H * W + 255) / 256, B);
   // both alphas 0: the instantiation without mixing, whose output does not depend on cfg
   const bool mixing = mix_enabled(cfg);
@@ -1714,10 +1794,16 @@ void augment_launch(const unsigned char* imgs, const long long* idx, long long i
   if (!(cfg.mixup_alpha >= 0.f && cfg.cutmix_alpha >= 0.f && cfg.prob >= 0.f && cfg.prob <= 1.f &&
         cfg.switch_prob >= 0.f && cfg.switch_prob <= 1.f))
     throw std::runtime_error("augment: mix alphas >= 0 and probabilities in [0, 1]");
-  auto kern = mixing ? augment_kernel<true> : augment_kernel<false>;
+  // prob 0: the instantiations without erasing, the kernels of a launch without these arguments
+  const bool erasing = erase_enabled(ecfg);
+  if (!erase_cfg_ok(ecfg)) throw std::runtime_error(std::string("augment") + kEraseCfgMsg);
+  if (erasing && (!erase || C != 3))
+    throw std::runtime_error("augment: erasing needs the erase rows and 3-channel images");
+  auto kern = mixing ? (erasing ? augment_kernel<true, true> : augment_kernel<true, false>)
+                     : (erasing ? augment_kernel<false, true> : augment_kernel<false, false>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, imgs, idx, idx_off, B, H, W, C, mean[0], mean[1], mean[2],
                      inv_std[0], inv_std[1], inv_std[2], pad, flip ? 1 : 0, counter, seed, out, nbatches, labels,
-                     labels_out, cfg, mix, labels_b);
+                     labels_out, cfg, mix, labels_b, ecfg, erase);
 }
 void mix_params_launch(unsigned long long seed, long long first, long long n, const MixCfg& cfg, int H, int W,
                        float* mix, hipStream_t st) {
@@ -1738,7 +1824,7 @@ void augment_resize_launch(const unsigned char* imgs, const long long* idx, long
                            const RrcCfg& rc, double center_frac, bool flip, const long long* counter,
                            unsigned long long seed, float* out, hipStream_t st, long long nbatches,
                            const long long* labels, long long* labels_out, int* crops, const MixCfg& cfg, float* mix,
-                           long long* labels_b) {
+                           long long* labels_b, const EraseCfg& ecfg, int* erase) {
   if (C != 3) throw std::runtime_error("augment_resize: 3-channel images only");
   if (B < 1 || B > 65535 || H < 1 || W < 1 || OH < 1 || OW < 1 || H > 0x7fff || W > 0x7fff || OH > 0x7fff || OW > 0x7fff)
     throw std::runtime_error("augment_resize: 1 <= batch < 65536 and 1 <= H, W, out_h, out_w < 32768");
@@ -1762,10 +1848,31 @@ void augment_resize_launch(const unsigned char* imgs, const long long* idx, long
   int gx = (passes + 3) / 4;
   if ((long long)gx * B < 512) gx = std::min(passes, (512 + B - 1) / B);
   const int vec = (OW % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
-  auto kern = mixing ? augment_resize_kernel<true> : augment_resize_kernel<false>;
+  const bool erasing = erase_enabled(ecfg);
+  if (!erase_cfg_ok(ecfg)) throw std::runtime_error(std::string("augment_resize") + kEraseCfgMsg);
+  if (erasing && !erase) throw std::runtime_error("augment_resize: erasing needs the erase rows");
+  auto kern = mixing ? (erasing ? augment_resize_kernel<true, true> : augment_resize_kernel<true, false>)
+                     : (erasing ? augment_resize_kernel<false, true> : augment_resize_kernel<false, false>);
   hipLaunchKernelGGL(kern, dim3(gx, B), dim3(256), 0, st, imgs, idx, idx_off, B, H, W, OH, OW, mean[0], mean[1],
                      mean[2], inv_std[0], inv_std[1], inv_std[2], train ? 1 : 0, rc, eh, ew, flip ? 1 : 0, counter,
-                     seed, out, nbatches, labels, labels_out, crops, cfg, mix, labels_b, vec);
+                     seed, out, nbatches, labels, labels_out, crops, cfg, mix, labels_b, vec, ecfg, erase);
+}
+void erase_params_launch(unsigned long long seed, long long first, long long n, int B, const EraseCfg& ecfg, int H,
+                         int W, int* rows, hipStream_t st) {
+  if (n <= 0 || B <= 0) return;
+  if (!erase_cfg_ok(ecfg) || H < 1 || W < 1 || H > 0x7fff || W > 0x7fff)
+    throw std::runtime_error(std::string("erase_params: 1 <= H, W < 32768") + kEraseCfgMsg);
+  const long long total = n * B;
+  hipLaunchKernelGGL(erase_params_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, seed, first, total,
+                     B, ecfg, H, W, rows);
+}
+void erase_noise_launch(unsigned long long seed, long long counter, int B, int H, int W, float* out, hipStream_t st) {
+  if (B <= 0) return;
+  if (B > 65535 || H < 1 || W < 1 || H > 0x7fff || W > 0x7fff)
+    throw std::runtime_error("erase_noise: batch < 65536 and 1 <= H, W < 32768");
+  const long long per3 = 3LL * H * W;
+  hipLaunchKernelGGL(erase_noise_kernel, dim3(grid_for(per3 * B)), dim3(256), 0, st, seed,
+                     (unsigned long long)counter, per3 * B, per3, out);
 }
 void rrc_params_launch(unsigned long long seed, long long first, long long n, int B, const RrcCfg& rc, int H, int W,
                        int* win, hipStream_t st) {

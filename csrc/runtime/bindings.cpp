@@ -177,11 +177,16 @@ PYBIND11_MODULE(_C, m) {
         py::arg("out") = py::none(), py::arg("nbatches") = 0, py::arg("labels") = py::none(),
         py::arg("labels_out") = py::none(), py::arg("mixup_alpha") = 0.0, py::arg("cutmix_alpha") = 0.0,
         py::arg("mix_prob") = 1.0, py::arg("mix_switch_prob") = 0.5, py::arg("mix") = py::none(),
-        py::arg("labels_b") = py::none(),
+        py::arg("labels_b") = py::none(), py::arg("erase_prob") = 0.0,
+        py::arg("erase_scale") = std::vector<double>{0.02, 0.33},
+        py::arg("erase_ratio") = std::vector<double>{0.3, 3.3}, py::arg("erase_mode") = "const",
+        py::arg("erase_value") = std::vector<double>{0.0}, py::arg("erase") = py::none(),
         "gather + RandomCrop + flip + normalize one batch (NHWC fp32); nbatches > 0 takes the batch offset from "
         "the step counter; labels_out receives the batch's labels; an alpha > 0 mixes image b with image "
         "batch - 1 - b (mixup / CutMix), publishing {mode, lam, lam_raw, y0, y1, x0, x1, 0} in mix and the "
-        "partners' labels in labels_b");
+        "partners' labels in labels_b; erase_prob > 0 erases a box of every image with that probability before "
+        "the mix (RandomErasing; mode const / rand / pixel), publishing {on, top, left, h, w} per image in erase "
+        "(int32 [batch, 5])");
   m.def("mix_params", &mix_params, py::arg("seed"), py::arg("first_counter"), py::arg("n"),
         py::arg("mixup_alpha") = 0.0, py::arg("cutmix_alpha") = 0.0, py::arg("mix_prob") = 1.0,
         py::arg("mix_switch_prob") = 0.5, py::arg("H") = 32, py::arg("W") = 32,
@@ -192,14 +197,25 @@ PYBIND11_MODULE(_C, m) {
         py::arg("seed"), py::arg("out") = py::none(), py::arg("nbatches") = 0, py::arg("labels") = py::none(),
         py::arg("labels_out") = py::none(), py::arg("crops"), py::arg("mixup_alpha") = 0.0,
         py::arg("cutmix_alpha") = 0.0, py::arg("mix_prob") = 1.0, py::arg("mix_switch_prob") = 0.5,
-        py::arg("mix") = py::none(), py::arg("labels_b") = py::none(),
+        py::arg("mix") = py::none(), py::arg("labels_b") = py::none(), py::arg("erase_prob") = 0.0,
+        py::arg("erase_scale") = std::vector<double>{0.02, 0.33},
+        py::arg("erase_ratio") = std::vector<double>{0.3, 3.3}, py::arg("erase_mode") = "const",
+        py::arg("erase_value") = std::vector<double>{0.0}, py::arg("erase") = py::none(),
         "gather + RandomResizedCrop (train) or central crop of center_frac + bilinear resize to out_h x out_w + "
         "flip + normalize one batch (NHWC fp32, 3 channels); crops (int32 [batch, 5]) receives {top, left, h, w, "
-        "flip} per image; idx, nbatches, labels and the mix arguments as augment (the CutMix box in output pixels)");
+        "flip} per image; idx, nbatches, labels, the mix and the erase arguments as augment (the CutMix and erase boxes "
+        "in output pixels)");
   m.def("rrc_params", &rrc_params, py::arg("seed"), py::arg("first_counter"), py::arg("n"), py::arg("B"),
         py::arg("scale"), py::arg("ratio"), py::arg("H"), py::arg("W"),
         "int32 [n, B, 4]: the windows {top, left, h, w} augment_resize draws at step counters first_counter .. "
         "first_counter + n - 1");
+  m.def("erase_params", &erase_params, py::arg("seed"), py::arg("first_counter"), py::arg("n"), py::arg("B"),
+        py::arg("prob"), py::arg("scale"), py::arg("ratio"), py::arg("H"), py::arg("W"),
+        "int32 [n, B, 5]: the erase rows {on, top, left, h, w} augment / augment_resize publish at step counters "
+        "first_counter .. first_counter + n - 1 for an H x W output");
+  m.def("erase_noise", &erase_noise, py::arg("seed"), py::arg("counter"), py::arg("B"), py::arg("H"), py::arg("W"),
+        "float32 [B, 3, H, W] channels_last: the N(0, 1) fill noise of the erase modes rand and pixel at one "
+        "step counter");
   m.def("counter_inc", &counter_inc);
   m.def("stack_mean", &stack_mean);
   m.def("scale_", &scale_);

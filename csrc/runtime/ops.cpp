@@ -2483,6 +2483,44 @@ MixCfg mix_cfg(double mixup_alpha, double cutmix_alpha, double prob, double swit
               ": mix_prob and mix_switch_prob must be in [0, 1]");
   return MixCfg{(float)mixup_alpha, (float)cutmix_alpha, (float)prob, (float)switch_prob};
 }
+// RandomErasing: scale and ratio are (lo, hi) pairs (the ratio is h / w), mode is const / rand / pixel, value a
+// float or three (normalised units, read under const)
+EraseCfg erase_cfg(double prob, const std::vector<double>& scale, const std::vector<double>& ratio,
+                   const std::string& mode, const std::vector<double>& value, const char* op) {
+  TORCH_CHECK(prob >= 0.0 && prob <= 1.0, op, ": erase_prob must be in [0, 1]. Got: ", prob);
+  TORCH_CHECK(scale.size() == 2 && ratio.size() == 2, op, ": erase_scale and erase_ratio are (lo, hi) pairs");
+  TORCH_CHECK(0.0 < scale[0] && scale[0] <= scale[1] && scale[1] <= 1.0, op,
+              ": 0 < erase_scale lo <= hi <= 1 required. Got: ", scale[0], ", ", scale[1]);
+  TORCH_CHECK(0.0 < ratio[0] && ratio[0] <= ratio[1] && std::isfinite(ratio[1]), op,
+              ": 0 < erase_ratio lo <= hi required. Got: ", ratio[0], ", ", ratio[1]);
+  TORCH_CHECK(mode == "const" || mode == "rand" || mode == "pixel", op,
+              ": erase_mode must be const, rand or pixel. Got: ", mode);
+  TORCH_CHECK(value.size() == 1 || value.size() == 3, op, ": erase_value is one float or three");
+  EraseCfg e;
+  e.prob = (float)prob;
+  e.scale_lo = (float)scale[0];
+  e.scale_hi = (float)scale[1];
+  e.log_ratio_lo = (float)std::log(ratio[0]);
+  e.log_ratio_hi = (float)std::log(ratio[1]);
+  e.mode = mode == "const" ? kEraseConst : (mode == "rand" ? kEraseRand : kErasePixel);
+  for (int c = 0; c < 3; ++c) {
+    const double v = value[std::min<size_t>(c, value.size() - 1)];
+    TORCH_CHECK(std::isfinite(v), op, ": erase_value must be finite");
+    e.value[c] = (float)v;
+  }
+  return e;
+}
+// the int32 [batch, 5] tensor that receives the erase rows (needed when erasing is on)
+int* erase_rows(const EraseCfg& e, const c10::optional<at::Tensor>& erase, const at::Tensor& images, int64_t batch,
+                const char* op) {
+  if (!erase_enabled(e)) return nullptr;
+  TORCH_CHECK(images.size(3) == 3, op, ": erasing needs 3-channel images. Got: ", images.size(3));
+  TORCH_CHECK(erase.has_value() && erase->defined() && erase->device() == images.device() &&
+                  erase->scalar_type() == at::kInt && erase->is_contiguous() && erase->dim() == 2 &&
+                  erase->size(0) == batch && erase->size(1) == kEraseRow,
+              op, ": erasing needs erase, a contiguous int32 [batch, 5] tensor on the images' device");
+  return erase->data_ptr<int>();
+}
 }  // namespace
 at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& indices, int64_t idx_offset, int64_t batch,
                    std::vector<double> mean, std::vector<double> std_, int64_t pad, bool flip,
@@ -2490,7 +2528,9 @@ at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& in
                    int64_t nbatches, const c10::optional<at::Tensor>& labels,
                    const c10::optional<at::Tensor>& labels_out, double mixup_alpha, double cutmix_alpha,
                    double mix_prob, double mix_switch_prob, const c10::optional<at::Tensor>& mix,
-                   const c10::optional<at::Tensor>& labels_b) {
+                   const c10::optional<at::Tensor>& labels_b, double erase_prob, std::vector<double> erase_scale,
+                   std::vector<double> erase_ratio, const std::string& erase_mode, std::vector<double> erase_value,
+                   const c10::optional<at::Tensor>& erase) {
   TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.dim() == 4,
               "images must be uint8 [N, H, W, C] on the GPU");
   const int H = images.size(1), W = images.size(2), C = images.size(3);
@@ -2550,8 +2590,12 @@ at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& in
       lb = reinterpret_cast<long long*>(labels_b->data_ptr<int64_t>());
     }
   }
+  // RandomErasing: on with erase_prob > 0; then image b's row {on, top, left, h, w} is published in erase[b]
+  const EraseCfg ecfg = erase_cfg(erase_prob, erase_scale, erase_ratio, erase_mode, erase_value, "augment");
+  int* ep = erase_rows(ecfg, erase, images, batch, "augment");
   augment_launch(images.data_ptr<uint8_t>(), ip, idx_offset, (int)batch, H, W, C, m, is, (int)pad, flip, cp,
-                 (unsigned long long)seed, o.data_ptr<float>(), cur_stream(), nbatches, lp, lo, cfg, mixp, lb);
+                 (unsigned long long)seed, o.data_ptr<float>(), cur_stream(), nbatches, lp, lo, cfg, mixp, lb, ecfg,
+                 ep);
   return o;
 }
 
@@ -2581,7 +2625,10 @@ at::Tensor augment_resize(const at::Tensor& images, const c10::optional<at::Tens
                           c10::optional<at::Tensor> out, int64_t nbatches, const c10::optional<at::Tensor>& labels,
                           const c10::optional<at::Tensor>& labels_out, const at::Tensor& crops, double mixup_alpha,
                           double cutmix_alpha, double mix_prob, double mix_switch_prob,
-                          const c10::optional<at::Tensor>& mix, const c10::optional<at::Tensor>& labels_b) {
+                          const c10::optional<at::Tensor>& mix, const c10::optional<at::Tensor>& labels_b,
+                          double erase_prob, std::vector<double> erase_scale, std::vector<double> erase_ratio,
+                          const std::string& erase_mode, std::vector<double> erase_value,
+                          const c10::optional<at::Tensor>& erase) {
   TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.dim() == 4 && images.is_contiguous(),
               "augment_resize: images must be contiguous uint8 [N, H, W, C] on the GPU");
   const int64_t H = images.size(1), W = images.size(2), C = images.size(3);
@@ -2657,9 +2704,12 @@ at::Tensor augment_resize(const at::Tensor& images, const c10::optional<at::Tens
       lb = reinterpret_cast<long long*>(labels_b->data_ptr<int64_t>());
     }
   }
+  const EraseCfg ecfg = erase_cfg(erase_prob, erase_scale, erase_ratio, erase_mode, erase_value, "augment_resize");
+  int* ep = erase_rows(ecfg, erase, images, batch, "augment_resize");
   augment_resize_launch(images.data_ptr<uint8_t>(), ip, idx_offset, (int)batch, (int)H, (int)W, (int)C, (int)out_h,
                         (int)out_w, m, is, train, rc, center_frac, flip, cp, (unsigned long long)seed,
-                        o.data_ptr<float>(), cur_stream(), nbatches, lp, lo, crops.data_ptr<int>(), cfg, mixp, lb);
+                        o.data_ptr<float>(), cur_stream(), nbatches, lp, lo, crops.data_ptr<int>(), cfg, mixp, lb,
+                        ecfg, ep);
   return o;
 }
 
@@ -2671,6 +2721,26 @@ at::Tensor rrc_params(int64_t seed, int64_t first_counter, int64_t n, int64_t B,
   at::Tensor out = at::empty({n, B, 4}, at::TensorOptions().dtype(at::kInt).device(at::kCUDA));
   rrc_params_launch((unsigned long long)seed, first_counter, n, (int)B, rc, (int)H, (int)W, out.data_ptr<int>(),
                     cur_stream());
+  return out;
+}
+
+at::Tensor erase_params(int64_t seed, int64_t first_counter, int64_t n, int64_t B, double prob,
+                        std::vector<double> scale, std::vector<double> ratio, int64_t H, int64_t W) {
+  TORCH_CHECK(n >= 0 && B >= 0 && B <= 65535 && H >= 1 && W >= 1 && H <= 0x7fff && W <= 0x7fff,
+              "erase_params: n >= 0, 0 <= B < 65536, 1 <= H, W < 32768");
+  const EraseCfg ecfg = erase_cfg(prob, scale, ratio, "const", {0.0}, "erase_params");
+  at::Tensor out = at::empty({n, B, kEraseRow}, at::TensorOptions().dtype(at::kInt).device(at::kCUDA));
+  erase_params_launch((unsigned long long)seed, first_counter, n, (int)B, ecfg, (int)H, (int)W, out.data_ptr<int>(),
+                      cur_stream());
+  return out;
+}
+
+at::Tensor erase_noise(int64_t seed, int64_t counter, int64_t B, int64_t H, int64_t W) {
+  TORCH_CHECK(B >= 0 && B <= 65535 && H >= 1 && W >= 1 && H <= 0x7fff && W <= 0x7fff,
+              "erase_noise: 0 <= B < 65536, 1 <= H, W < 32768");
+  at::Tensor out = at::empty({B, 3, H, W}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA).memory_format(
+                                               at::MemoryFormat::ChannelsLast));
+  erase_noise_launch((unsigned long long)seed, counter, (int)B, (int)H, (int)W, out.data_ptr<float>(), cur_stream());
   return out;
 }
 

@@ -182,13 +182,17 @@ at::Tensor augment(const at::Tensor& images, const c10::optional<at::Tensor>& in
                    const c10::optional<at::Tensor>& labels_out = c10::nullopt, double mixup_alpha = 0.0,
                    double cutmix_alpha = 0.0, double mix_prob = 1.0, double mix_switch_prob = 0.5,
                    const c10::optional<at::Tensor>& mix = c10::nullopt,
-                   const c10::optional<at::Tensor>& labels_b = c10::nullopt);
+                   const c10::optional<at::Tensor>& labels_b = c10::nullopt, double erase_prob = 0.0,
+                   std::vector<double> erase_scale = {0.02, 0.33}, std::vector<double> erase_ratio = {0.3, 3.3},
+                   const std::string& erase_mode = "const", std::vector<double> erase_value = {0.0},
+                   const c10::optional<at::Tensor>& erase = c10::nullopt);
 // float32 [n, 8]: the rows {mode, lam, lam_raw, y0, y1, x0, x1, 0} augment publishes at counters first_counter + i
 at::Tensor mix_params(int64_t seed, int64_t first_counter, int64_t n, double mixup_alpha, double cutmix_alpha,
                       double mix_prob, double mix_switch_prob, int64_t H, int64_t W);
 // The augment launch with a resize (3-channel images): RandomResizedCrop (train; scale and ratio are (lo, hi) pairs)
 // or the central window of fraction center_frac, resampled bilinearly to out_h x out_w, then flip / normalise /
-// mix as augment. crops: int32 [batch, 5], receives {top, left, h, w, flip} per image.
+// mix / erase as augment (the erase box in output pixels). crops: int32 [batch, 5], receives {top, left, h, w, flip}
+// per image.
 at::Tensor augment_resize(const at::Tensor& images, const c10::optional<at::Tensor>& indices, int64_t idx_offset,
                           int64_t batch, std::vector<double> mean, std::vector<double> std_, int64_t out_h,
                           int64_t out_w, bool train, std::vector<double> scale, std::vector<double> ratio,
@@ -197,10 +201,19 @@ at::Tensor augment_resize(const at::Tensor& images, const c10::optional<at::Tens
                           const c10::optional<at::Tensor>& labels_out, const at::Tensor& crops,
                           double mixup_alpha = 0.0, double cutmix_alpha = 0.0, double mix_prob = 1.0,
                           double mix_switch_prob = 0.5, const c10::optional<at::Tensor>& mix = c10::nullopt,
-                          const c10::optional<at::Tensor>& labels_b = c10::nullopt);
+                          const c10::optional<at::Tensor>& labels_b = c10::nullopt, double erase_prob = 0.0,
+                          std::vector<double> erase_scale = {0.02, 0.33}, std::vector<double> erase_ratio = {0.3, 3.3},
+                          const std::string& erase_mode = "const", std::vector<double> erase_value = {0.0},
+                          const c10::optional<at::Tensor>& erase = c10::nullopt);
 // int32 [n, B, 4]: the windows {top, left, h, w} augment_resize draws at counters first_counter + i for image slot b
 at::Tensor rrc_params(int64_t seed, int64_t first_counter, int64_t n, int64_t B, std::vector<double> scale,
                       std::vector<double> ratio, int64_t H, int64_t W);
+// int32 [n, B, 5]: the rows {on, top, left, h, w} the augment launches publish at counters first_counter + i for
+// image slot b of an H x W output (RandomErasing, erase_prob = prob)
+at::Tensor erase_params(int64_t seed, int64_t first_counter, int64_t n, int64_t B, double prob,
+                        std::vector<double> scale, std::vector<double> ratio, int64_t H, int64_t W);
+// float32 [B, 3, H, W] channels_last: the N(0, 1) fill noise of the erase modes rand and pixel at one counter
+at::Tensor erase_noise(int64_t seed, int64_t counter, int64_t B, int64_t H, int64_t W);
 void counter_inc(at::Tensor c);
 void stack_mean(const std::vector<at::Tensor>& srcs, at::Tensor dst);
 void gpu_sleep(double us);
