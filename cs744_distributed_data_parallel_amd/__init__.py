@@ -18,7 +18,7 @@ Typical use (mirrors the reference API)::
 from . import _native, data, distributed, models, ops, optim, parallel, utils
 from .data import MixTarget
 from .models import VGG11, VGG13, VGG16, VGG19, ResNet, get_model, resnet18, resnet34, resnet50, resnet101, resnet152
-from .ops import CrossEntropyLoss
+from .ops import BinaryCrossEntropy, CrossEntropyLoss
 from .optim import LAMB, LARS, SGD, AdamW, LRSchedule, clip_grad_norm_
 from .parallel import DDP, DistributedDataParallel
 
@@ -27,7 +27,7 @@ __version__ = "0.1.0"
 __all__ = [
     "_native", "data", "distributed", "models", "ops", "optim", "parallel", "utils",
     "VGG11", "VGG13", "VGG16", "VGG19", "get_model", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
-    "resnet152", "CrossEntropyLoss", "MixTarget", "SGD", "LARS", "AdamW", "LAMB", "LRSchedule", "clip_grad_norm_",
+    "resnet152", "CrossEntropyLoss", "BinaryCrossEntropy", "MixTarget", "SGD", "LARS", "AdamW", "LAMB", "LRSchedule", "clip_grad_norm_",
     "DDP", "DistributedDataParallel", "native_available",
 ]
 

@@ -23,6 +23,7 @@ __all__ = [
     "conv_bn_act",
     "linear",
     "cross_entropy",
+    "binary_cross_entropy",
     "max_pool2d",
     "global_avg_pool",
     "use_native",
@@ -369,6 +370,27 @@ def linear(x, weight, bias=None):
 
 
 # --------------------------------------------------------------------------- cross entropy
+def _fused_classifier_bwd(lin, g, logits, target, **loss_args):
+    """The loss's gradient and the narrow native Linear's backward (``lin``: its autograd node) in one launch,
+    with the BN statistics hand-off of the block that produced the Linear's input; parks the Linear's gradients
+    in ``lin.fused`` and returns dlogits. ``loss_args``: the loss's keyword arguments of ``xent_linear_bwd``."""
+    x, w = lin.saved_tensors
+    wp, bp = lin.params
+    nig = lin.needs_input_grad
+    has_b = lin.has_bias
+    li, lin.link_in = lin.link_in, None
+    link = li is not None and li.consumers == 1 and nig[0] and li.y.shape[2] == li.y.shape[3] == (
+        2 if li.pool else 1)
+    dl, dx, dw, db, part = _native.lib().xent_linear_bwd(
+        g.reshape(1), logits, target, x, w, nig[0], has_b, _slot(wp, nig[1]), _slot(bp, nig[2] and has_b),
+        li.y if link else None, li.stats if link else None, bool(li.pool) if link else False,
+        bool(li.relu) if link else False, li.ps if link else 2, **loss_args)
+    if link:  # the producer block's backward takes these partials if its gradient is this dX
+        li.part, li.gptr, li.gver = part, dx.data_ptr(), dx._version
+    lin.fused = (dl, dx if nig[0] else None, dw, db if has_b else None)
+    return dl
+
+
 class _XEnt(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, label_smoothing=0.0, target_b=None, lam=None):
@@ -387,21 +409,7 @@ class _XEnt(torch.autograd.Function):
         logits, target, target_b, lam = ctx.saved_tensors
         lin, ctx.lin = ctx.lin, None
         if lin is not None and os.environ.get("CDP_FUSED_CLASSIFIER", "1") != "0":
-            x, w = lin.saved_tensors
-            wp, bp = lin.params
-            nig = lin.needs_input_grad
-            has_b = lin.has_bias
-            li, lin.link_in = lin.link_in, None
-            link = li is not None and li.consumers == 1 and nig[0] and li.y.shape[2] == li.y.shape[3] == (
-                2 if li.pool else 1)
-            dl, dx, dw, db, part = _native.lib().xent_linear_bwd(
-                g.reshape(1), logits, target, x, w, nig[0], has_b, _slot(wp, nig[1]), _slot(bp, nig[2] and has_b),
-                li.y if link else None, li.stats if link else None, bool(li.pool) if link else False,
-                bool(li.relu) if link else False, li.ps if link else 2, label_smoothing=ctx.eps,
-                target_b=target_b, lam=lam)
-            if link:  # the producer block's backward takes these partials if its gradient is this dX
-                li.part, li.gptr, li.gver = part, dx.data_ptr(), dx._version
-            lin.fused = (dl, dx if nig[0] else None, dw, db if has_b else None)
+            dl = _fused_classifier_bwd(lin, g, logits, target, label_smoothing=ctx.eps, target_b=target_b, lam=lam)
             return dl, None, None, None, None
         return _native.lib().xent_bwd(g.reshape(1), logits, target, ctx.eps, target_b, lam), None, None, None, None
 
@@ -440,6 +448,111 @@ def cross_entropy(logits, target, label_smoothing=0.0, target_b=None, lam=None):
         lam = lam.reshape(()).to(logits.device)
     return (lam * F.cross_entropy(logits, target, label_smoothing=label_smoothing)
             + (1 - lam) * F.cross_entropy(logits, target_b, label_smoothing=label_smoothing))
+
+
+# --------------------------------------------------------------------------- binary cross entropy
+class _BCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, label_smoothing=0.0, target_threshold=None, sum_classes=False, target_b=None,
+                lam=None):
+        # as _XEnt: eps, the threshold and the reduction are host kernel arguments, lam is read on the device
+        ctx.save_for_backward(logits, target, target_b, lam)
+        ctx.knobs = (float(label_smoothing), None if target_threshold is None else float(target_threshold),
+                     bool(sum_classes))
+        node = logits.grad_fn
+        ctx.lin = node if (getattr(node, "narrow", False) and hasattr(node, "fused")
+                           and logits.shape[0] * logits.shape[1] <= _XENT_LIN_MAX) else None
+        return _native.lib().bce_fwd(logits, target, *ctx.knobs, target_b, lam)
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, target_b, lam = ctx.saved_tensors
+        eps, thr, sum_classes = ctx.knobs
+        lin, ctx.lin = ctx.lin, None
+        if lin is not None and os.environ.get("CDP_FUSED_CLASSIFIER", "1") != "0":
+            dl = _fused_classifier_bwd(lin, g, logits, target, label_smoothing=eps, target_b=target_b, lam=lam,
+                                       bce=True, target_threshold=thr, sum_classes=sum_classes)
+            return dl, None, None, None, None, None, None
+        return (_native.lib().bce_bwd(g.reshape(1), logits, target, eps, thr, sum_classes, target_b, lam),
+                None, None, None, None, None, None)
+
+
+def bce_dense_target(target, num_classes, label_smoothing=0.0, target_threshold=None, target_b=None, lam=None,
+                     dtype=torch.float32):
+    """The dense ``[B, C]`` target of :func:`binary_cross_entropy` with torch ops, in the kernels' order:
+    ``((onehot_a * wa) + (onehot_b * wb)) + off`` with ``wa = (1 - eps) * lam``, ``wb = (1 - eps) * (1 - lam)``,
+    ``off = eps / C`` (no second target: ``lam = 1``), then ``> target_threshold`` when given. An index out of
+    ``[0, C)`` matches no class."""
+    C = int(num_classes)
+    dev = target.device
+    one = torch.ones((), dtype=dtype, device=dev)
+    lam_t = one if lam is None else (lam.detach().reshape(()).to(device=dev, dtype=dtype) if torch.is_tensor(lam)
+                                     else one * float(lam))
+    on = one - torch.as_tensor(float(label_smoothing), dtype=dtype, device=dev)
+    off = torch.as_tensor(float(label_smoothing), dtype=dtype, device=dev) / C
+    cls = torch.arange(C, device=dev).unsqueeze(0)
+    y = (cls == target.reshape(-1, 1)).to(dtype) * (on * lam_t)
+    if target_b is not None:
+        y = y + (cls == target_b.reshape(-1, 1)).to(dtype) * (on * (one - lam_t))
+    y = y + off
+    if target_threshold is not None:
+        y = (y > target_threshold).to(dtype)
+    return y
+
+
+def binary_cross_entropy(logits, target, label_smoothing=0.0, target_threshold=None, sum_classes=False, target_b=None,
+                         lam=None):
+    """Binary cross-entropy with logits, every logit its own one-vs-rest classifier (timm's
+    ``BinaryCrossEntropy`` composed with its ``mixup_target``), against the dense target
+
+    ``y = (1 - label_smoothing) * (lam * onehot(target) + (1 - lam) * onehot(target_b)) + label_smoothing / C``
+
+    that is formed inside the kernels and never stored. ``target_threshold`` in [0, 1) binarises it
+    (``y > target_threshold``); the loss is the mean over all ``B * C`` elements, or with ``sum_classes`` the sum
+    over the classes and the mean over the batch. ``target_b`` and ``lam`` go together (mixup / CutMix); ``lam``
+    is a float or a 1-element tensor that the GPU kernels read from the device, so it may change between graph
+    replays.
+
+    A float ``target`` of the logits' shape is the dense (multi-label) form and always takes the PyTorch
+    composition (``label_smoothing`` / ``target_b`` do not apply to it; the threshold and the reduction do)."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
+    if target_threshold is not None and not 0.0 <= target_threshold < 1.0:
+        raise ValueError(f"target_threshold must be in [0.0, 1.0). Got: {target_threshold}")
+    if (target_b is None) != (lam is None):
+        raise ValueError("binary_cross_entropy: target_b and lam must be given together")
+    if lam is not None:
+        if torch.is_tensor(lam):
+            if lam.numel() != 1:
+                raise ValueError(
+                    f"binary_cross_entropy: lam must hold one element (one lam per batch). Got: {tuple(lam.shape)}")
+        elif not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam must be between 0.0 and 1.0. Got: {lam}")
+
+    def reduce(per_elem):
+        return per_elem.sum(-1).mean() if sum_classes else per_elem.mean()
+
+    if target.is_floating_point():
+        if target.shape != logits.shape:
+            raise ValueError(f"binary_cross_entropy: a dense target has the logits' shape. Got: {tuple(target.shape)} "
+                             f"for {tuple(logits.shape)}")
+        if target_b is not None or label_smoothing != 0.0:
+            raise ValueError("binary_cross_entropy: label_smoothing and target_b belong to index targets")
+        y = target.to(logits.dtype)
+        if target_threshold is not None:
+            y = (y > target_threshold).to(logits.dtype)
+        return reduce(F.binary_cross_entropy_with_logits(logits, y, reduction="none"))
+    if use_native(logits) and logits.dim() == 2 and logits.dtype == torch.float32:
+        if lam is not None:
+            if not torch.is_tensor(lam):
+                lam = torch.full((1,), float(lam), dtype=torch.float32, device=logits.device)
+            elif lam.dtype != torch.float32 or lam.device != logits.device:
+                lam = lam.to(device=logits.device, dtype=torch.float32)
+            lam = lam.detach().reshape(1)
+        return _BCE.apply(logits, target, float(label_smoothing), target_threshold, bool(sum_classes), target_b, lam)
+    C = logits.shape[-1]
+    y = bce_dense_target(target, C, label_smoothing, target_threshold, target_b, lam, dtype=logits.dtype)
+    return reduce(F.binary_cross_entropy_with_logits(logits, y.reshape(logits.shape), reduction="none"))
 
 
 def topk_hits(logits, target, topk):

@@ -29,7 +29,7 @@ import torch
 from . import distributed as dist
 from .data import MIX_MODES, DeviceLoader, DistributedSampler, MixTarget, cifar10_binary, synthetic_cifar10, synthetic_imagenet
 from .models import get_model
-from .ops import CrossEntropyLoss, count_correct
+from .ops import BinaryCrossEntropy, CrossEntropyLoss, count_correct
 from .optim import LAMB, LARS, SGD, AdamW, LRSchedule
 from .parallel import (
     BucketedOverlap,
@@ -211,7 +211,12 @@ def run(rank, size, epochs, batch_size, args):
         print(f"[cdp] rank {rank}: collectives on {kind}"
               + (f" ({dist.comm_fallback_reason()})" if dist.comm_fallback_reason() else ""), file=sys.stderr)
     # label smoothing shapes the training loss only: the eval loss stays the plain cross-entropy
-    criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
+    # (--loss bce: every logit a one-vs-rest sigmoid classifier, against the same smoothed / mixed targets)
+    if getattr(args, "loss", "ce") == "bce":
+        criterion = BinaryCrossEntropy(label_smoothing=args.label_smoothing, target_threshold=args.bce_target_thresh,
+                                       sum_classes=args.bce_sum_classes)
+    else:
+        criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
     eval_criterion = CrossEntropyLoss()
     model = get_model(args.model).to(device)
     sync = None
@@ -398,6 +403,14 @@ def parse_args(argv=None):
                         "evaluate it too after every epoch (stderr); checkpoints carry it")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="FLOAT",
                    help="train against (1 - FLOAT) * onehot + FLOAT / classes (the test loss stays unsmoothed)")
+    p.add_argument("--loss", default="ce", choices=["ce", "bce"],
+                   help="training loss: softmax cross-entropy (ce, the reference's) or binary cross-entropy with logits "
+                        "over the same index / mixed targets (bce); --label-smoothing feeds either, the test loss "
+                        "stays the plain cross-entropy")
+    p.add_argument("--bce-target-thresh", type=float, default=None, metavar="FLOAT",
+                   help="--loss bce: binarise the smoothed / mixed target, 1 where it is above FLOAT in [0, 1)")
+    p.add_argument("--bce-sum-classes", action="store_true",
+                   help="--loss bce: sum the loss over the classes and average over the batch (default: mean over both)")
     p.add_argument("--mixup-alpha", type=float, default=0.0, metavar="FLOAT",
                    help="mixup: blend every training batch with its reverse, lam ~ Beta(FLOAT, FLOAT) per batch (0: off)")
     p.add_argument("--cutmix-alpha", type=float, default=0.0, metavar="FLOAT",
@@ -440,7 +453,12 @@ def parse_args(argv=None):
                    help="CPU intra-op threads for the CPU path (the reference pins 4: src/Part 1/main.py:11)")
     p.add_argument("--reference-bn-quirk", action="store_true",
                    help="reproduce the reference's missing model.train() after the first eval")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.loss != "bce" and (args.bce_target_thresh is not None or args.bce_sum_classes):
+        p.error("--bce-target-thresh and --bce-sum-classes need --loss bce")
+    if args.bce_target_thresh is not None and not 0.0 <= args.bce_target_thresh < 1.0:
+        p.error("--bce-target-thresh must be in [0, 1)")
+    return args
 
 
 def main(argv=None):

@@ -305,6 +305,17 @@ void xent_fwd_launch(const float* logits, const long long* tgt, int B, int C, fl
                      const float* lam = nullptr);
 void xent_bwd_launch(const float* logits, const long long* tgt, const float* gscale, int B, int C, float* dlogits,
                      hipStream_t st, float eps = 0.f, const long long* tgt_b = nullptr, const float* lam = nullptr);
+// Binary cross-entropy with logits against the dense target of (tgt, tgt_b, lam, eps), formed in registers:
+// y = ((c == tgt ? (1 - eps) lam : 0) + (c == tgt_b ? (1 - eps) (1 - lam) : 0)) + eps / C; thr (host pointer or
+// null; in [0, 1)): y = y > *thr; loss = sum / (B C), or / B with sum_classes. One block, fp64 sums in a fixed
+// order; nothing allocated or zeroed. A target out of [0, C) makes the loss NaN and matches no class in the
+// gradient.
+void bce_fwd_launch(const float* logits, const long long* tgt, int B, int C, float* loss, hipStream_t st,
+                    float eps = 0.f, const float* thr = nullptr, bool sum_classes = false,
+                    const long long* tgt_b = nullptr, const float* lam = nullptr);
+void bce_bwd_launch(const float* logits, const long long* tgt, const float* gscale, int B, int C, float* dlogits,
+                    hipStream_t st, float eps = 0.f, const float* thr = nullptr, bool sum_classes = false,
+                    const long long* tgt_b = nullptr, const float* lam = nullptr);
 // counter (optional): a step counter the kernel advances by one (DeviceLoader.advance_with)
 void sgd_launch(float* p, const float* g, float* buf, long long n, const float* lr_ptr, float lr, float momentum,
                 float dampening, float wd, float grad_scale, bool nesterov, bool first, bool maximize,
@@ -407,6 +418,7 @@ void small_linear_bwd_launch(const float* dy, const float* x, const float* w, in
 // optionally with the BN backward partials of the block that produced the Linear's input
 // (y != nullptr: that block's pre-BN output [B][pool ? 2x2 : 1x1][C = I] NHWC, stats [4][C],
 // part [1][C][ps] out)
+// bce (with thr, sum_classes as bce_bwd_launch): the loss is the binary cross-entropy, dlogits bce_bwd's bits
 constexpr int kXentLinMax = 8192;
 constexpr int kXentLinRows = 32;  // dX rows per block (and per BN partial)
 inline int xent_lin_chunks(int B) { return (B + kXentLinRows - 1) / kXentLinRows; }
@@ -419,7 +431,8 @@ struct XentBnLink {
 void xent_linear_bwd_launch(const float* logits, const long long* tgt, const float* gscale, const float* x,
                             const float* w, int B, int I, int O, float* dlogits, float* dx, float* dw, float* db,
                             const XentBnLink& lk, hipStream_t st, float eps = 0.f, const long long* tgt_b = nullptr,
-                            const float* lam = nullptr);
+                            const float* lam = nullptr, bool bce = false, const float* thr = nullptr,
+                            bool sum_classes = false);
 void avgpool_fwd_launch(const float* x, int N, int HW, int C, float* y, hipStream_t st);
 void avgpool_bwd_launch(const float* gy, int N, int HW, int C, float* gx, hipStream_t st);
 // NHWC, C % 4 == 0; arg = window-local argmax tap (uint8, k*k <= 255)

@@ -1,4 +1,4 @@
-// Small fused kernels: softmax cross-entropy (fwd / bwd / accuracy), fused SGD, CIFAR-style
+// Small fused kernels: softmax and binary cross-entropy (fwd / bwd / accuracy), fused SGD, CIFAR-style
 // augmentation, weight transpose for conv data-gradients, stack-mean for the gather/scatter
 // strategy, and generic scale / channel-sum helpers. gfx950, wave64.
 //
@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
+#include <string>
 
 #include "act_max.h"
 #include "common.h"
@@ -315,6 +316,137 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
     else
       dlogits[(long long)r * C + c] = (sm - (c == t ? 1.f : 0.f)) * k;
   }
+}
+
+// ------------------------------------------------------------------ binary cross-entropy
+// Every logit its own one-vs-rest sigmoid classifier, against the dense target that mixup / CutMix and
+// label smoothing define, formed in registers from the row's two class indices and xent_mix_w's weights:
+//   y[r][c] = ((c == t_a ? wa : 0) + (c == t_b ? wb : 0)) + off     each + rounded on its own
+//   thr_on:  y = y > thr ? 1 : 0
+//   l = max(z, 0) - z y + log1p(exp(-|z|))                          finite for every finite z
+//   loss = sum l / (B C), or / B with sum_classes;  dz = (sigmoid(z) - y) * gscale / (B C), or / B
+// Without a second target lam = 1 and no class matches t_b: the arithmetic of lam[0] == 1.
+struct BceArgs {
+  float thr;
+  int thr_on, sum_classes;
+};
+__device__ __forceinline__ float bce_y(bool isa, bool isb, const XentMixW& w, const BceArgs& a) {
+  const float y = __fadd_rn(__fadd_rn(isa ? w.wa : 0.f, isb ? w.wb : 0.f), w.off);
+  return a.thr_on ? (y > a.thr ? 1.f : 0.f) : y;
+}
+__device__ __forceinline__ float bce_elem(float z, float y) {
+  return __fadd_rn(__fsub_rn(fmaxf(z, 0.f), __fmul_rn(z, y)), log1pf(expf(-fabsf(z))));
+}
+// sigmoid(z) from e = exp(-|z|) in (0, 1]: 1 / (1 + e) or e / (1 + e), in [0, 1] for every finite z
+__device__ __forceinline__ float bce_grad(float z, float y, float k) {
+  const float e = expf(-fabsf(z));
+  const float sg = __fdiv_rn(z >= 0.f ? 1.f : e, __fadd_rn(1.f, e));
+  return __fmul_rn(__fsub_rn(sg, y), k);
+}
+__device__ __forceinline__ float bce_k(float g, int B, int C, int sum_classes) {
+  return sum_classes ? g / (float)B : g / ((float)B * (float)C);
+}
+
+// One block of 1024 threads in xent_fwd_kernel's three row layouts (C <= 64: a row per thread; C <= 1024: a
+// wave's rows held in registers, two at a time; wider: a row per wave); every thread adds its elements in
+// fp64 in a fixed order, then the fp64 block reduction: one writer, the same bits on every run. A target
+// out of [0, C) in either slot adds a NaN.
+template <bool MIX>
+__global__ __launch_bounds__(1024) void bce_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ tgt,
+                                                      int B, int C, float* __restrict__ loss, float eps, BceArgs ba,
+                                                      const long long* __restrict__ tgt_b,
+                                                      const float* __restrict__ lam_p) {
+  __shared__ double red[16];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  double acc = 0.0;
+  float lam = 1.f;
+  if (MIX) lam = lam_p[0];
+  const XentMixW mw = xent_mix_w(lam, eps, C);
+  if (C <= 64) {
+    for (int r = tid; r < B; r += 1024) {
+      const float* row = logits + (long long)r * C;
+      const long long t = tgt[r];
+      long long tb = -1;
+      if (MIX) tb = tgt_b[r];
+      const bool ok = t >= 0 && t < C && (!MIX || (tb >= 0 && tb < C));
+      for (int c = 0; c < C; ++c) acc += (double)bce_elem(row[c], bce_y(c == t, c == tb, mw, ba));
+      if (!ok) acc += (double)NAN;
+    }
+  } else if (C <= 1024) {
+    // rows wid + 16 k two at a time, all loaded before the first is used (as xent_fwd_kernel's four; two keep
+    // the exp / log1p temporaries beside the tile within the 128 registers of a 1024-thread block)
+    constexpr int RB = 2, J = 16;
+    for (int rb = wid; rb < B; rb += 16 * RB) {
+      float v[RB][J];
+#pragma unroll
+      for (int k = 0; k < RB; ++k) {
+        const int r = rb + 16 * k;
+        const float* row = logits + (long long)(r < B ? r : 0) * C;
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+          const int c = lane + 64 * j;
+          v[k][j] = (r < B && c < C) ? row[c] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < RB; ++k) {
+        const int r = rb + 16 * k;
+        if (r >= B) break;
+        const long long t = tgt[r];  // (one address per wave: a broadcast load)
+        long long tb = -1;
+        if (MIX) tb = tgt_b[r];
+        const bool ok = t >= 0 && t < C && (!MIX || (tb >= 0 && tb < C));
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+          const int c = lane + 64 * j;
+          if (c < C) acc += (double)bce_elem(v[k][j], bce_y(c == t, c == tb, mw, ba));
+        }
+        if (!ok && lane == 0) acc += (double)NAN;
+      }
+    }
+  } else {
+    for (int r = wid; r < B; r += 16) {
+      const float* row = logits + (long long)r * C;
+      const long long t = tgt[r];
+      long long tb = -1;
+      if (MIX) tb = tgt_b[r];
+      const bool ok = t >= 0 && t < C && (!MIX || (tb >= 0 && tb < C));
+      for (int c = lane; c < C; c += 64) acc += (double)bce_elem(row[c], bce_y(c == t, c == tb, mw, ba));
+      if (!ok && lane == 0) acc += (double)NAN;
+    }
+  }
+  acc = wave_sum_d(acc);
+  if (lane == 0) red[wid] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int i = 0; i < 16; ++i) s += red[i];
+    loss[0] = (float)(s / (ba.sum_classes ? (double)B : (double)B * (double)C));
+  }
+}
+
+// Elementwise, xent_bwd_kernel's block shape (a wave per row, four rows per block). A row with a target out
+// of range has no such class: no index matches. Every step rounded on its own (bce_y, bce_grad), so
+// xent_linear_bwd_kernel's BCE mode gives the same bits.
+template <bool MIX>
+__global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ tgt,
+                                                     const float* __restrict__ gscale, int B, int C,
+                                                     float* __restrict__ dlogits, float eps, BceArgs ba,
+                                                     const long long* __restrict__ tgt_b,
+                                                     const float* __restrict__ lam_p) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const float* row = logits + (long long)r * C;
+  const float k = bce_k(gscale[0], B, C, ba.sum_classes);
+  float lam = 1.f;
+  if (MIX) lam = lam_p[0];
+  const XentMixW mw = xent_mix_w(lam, eps, C);
+  const long long t = tgt[r];
+  long long tb = -1;
+  if (MIX) tb = tgt_b[r];
+  for (int c = lane; c < C; c += 64)
+    dlogits[(long long)r * C + c] = bce_grad(row[c], bce_y(c == t, c == tb, mw, ba), k);
 }
 
 // ------------------------------------------------------------------ SGD (torch semantics)
@@ -1396,7 +1528,10 @@ __global__ __launch_bounds__(256) void small_linear_bwd_kernel(const float* __re
 // xent_bwd_kernel<true>; the sdy tile then carries the smoothed gradient and nothing else differs.
 // MIX (tgt_b, lam: xent_bwd_kernel<., true>'s gradient, bit for bit, for every eps): the butterfly sum
 // order whatever eps is, and xent_mix_grad's rounding steps.
-template <bool LS, bool MIX>
+// BCE (binary cross-entropy, bce_bwd_kernel<MIX>'s gradient, bit for bit): only the rows' dlogits differ,
+// dlogits = (sigmoid(z) - y) * gscale / (B O), or / B; no softmax, so nothing is reduced over the classes.
+// LS is not read (eps is: it shapes y). The instantiations without BCE do not read ba.
+template <bool LS, bool MIX, bool BCE = false>
 __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __restrict__ logits,
                                                               const long long* __restrict__ tgt,
                                                               const float* __restrict__ gscale,
@@ -1405,14 +1540,26 @@ __global__ __launch_bounds__(256) void xent_linear_bwd_kernel(const float* __res
                                                               float* __restrict__ dx, float* __restrict__ dw,
                                                               float* __restrict__ db, int nbx, int nbw, XentBnLink lk,
                                                               float eps, const long long* __restrict__ tgt_b,
-                                                              const float* __restrict__ lam_p) {
+                                                              const float* __restrict__ lam_p, BceArgs ba) {
   __shared__ float sdy[kXentLinMax];
-  const float k = gscale[0] / (float)B;
+  const float k = BCE ? bce_k(gscale[0], B, O, ba.sum_classes) : gscale[0] / (float)B;
   const float on = 1.f - eps, off = eps / (float)O;  // (LS only)
   XentMixW mw{0.f, 0.f, 0.f};
   if (MIX) mw = xent_mix_w(lam_p[0], eps, O);
+  else if (BCE) mw = xent_mix_w(1.f, eps, O);
   for (int r = threadIdx.x; r < B; r += 256) {
     const float* row = logits + (long long)r * O;
+    if (BCE) {
+      const long long t = tgt[r];
+      long long tb = -1;
+      if (MIX) tb = tgt_b[r];
+      for (int o = 0; o < O; ++o) {
+        const float d = bce_grad(row[o], bce_y(o == t, o == tb, mw, ba), k);
+        sdy[r * O + o] = d;
+        if (blockIdx.x == 0) dlogits[(long long)r * O + o] = d;
+      }
+      continue;
+    }
     float v[SL_MAXO];
     float mx = -INFINITY;
 #pragma unroll
@@ -1684,6 +1831,30 @@ void xent_bwd_launch(const float* logits, const long long* tgt, const float* gsc
   auto kern = tgt_b ? (eps != 0.f ? xent_bwd_kernel<true, true> : xent_bwd_kernel<false, true>)
                     : (eps != 0.f ? xent_bwd_kernel<true, false> : xent_bwd_kernel<false, false>);
   hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, st, logits, tgt, gscale, B, C, dlogits, eps, tgt_b, lam);
+}
+namespace {
+BceArgs bce_args(const char* op, float eps, const float* thr, bool sum_classes, const long long* tgt_b,
+                 const float* lam) {
+  const std::string o(op);
+  if (!(eps >= 0.f && eps <= 1.f)) throw std::runtime_error(o + ": label smoothing in [0, 1]");
+  if (thr && !(*thr >= 0.f && *thr < 1.f)) throw std::runtime_error(o + ": target threshold in [0, 1)");
+  if ((tgt_b != nullptr) != (lam != nullptr)) throw std::runtime_error(o + ": tgt_b and lam go together");
+  return BceArgs{thr ? *thr : 0.f, thr ? 1 : 0, sum_classes ? 1 : 0};
+}
+}  // namespace
+void bce_fwd_launch(const float* logits, const long long* tgt, int B, int C, float* loss, hipStream_t st, float eps,
+                    const float* thr, bool sum_classes, const long long* tgt_b, const float* lam) {
+  const BceArgs ba = bce_args("bce_fwd", eps, thr, sum_classes, tgt_b, lam);
+  auto kern = tgt_b ? bce_fwd_kernel<true> : bce_fwd_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, st, logits, tgt, B, C, loss, eps, ba, tgt_b, lam);
+}
+void bce_bwd_launch(const float* logits, const long long* tgt, const float* gscale, int B, int C, float* dlogits,
+                    hipStream_t st, float eps, const float* thr, bool sum_classes, const long long* tgt_b,
+                    const float* lam) {
+  const BceArgs ba = bce_args("bce_bwd", eps, thr, sum_classes, tgt_b, lam);
+  if (B <= 0) return;
+  auto kern = tgt_b ? bce_bwd_kernel<true> : bce_bwd_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, st, logits, tgt, gscale, B, C, dlogits, eps, ba, tgt_b, lam);
 }
 void lr_sched_advance_launch(const SchedArgs& sched, const float* lr_ptr, float lr, hipStream_t st) {
   if (!sched.state || !sched.cfg) throw std::runtime_error("lr_sched_advance: state and cfg required");
@@ -2002,17 +2173,22 @@ void small_linear_bwd_launch(const float* dy, const float* x, const float* w, in
 void xent_linear_bwd_launch(const float* logits, const long long* tgt, const float* gscale, const float* x,
                             const float* w, int B, int I, int O, float* dlogits, float* dx, float* dw, float* db,
                             const XentBnLink& lk, hipStream_t st, float eps, const long long* tgt_b,
-                            const float* lam) {
+                            const float* lam, bool bce, const float* thr, bool sum_classes) {
   if (O > SL_MAXO || (long long)B * O > kXentLinMax) throw std::runtime_error("xent_linear_bwd: classifier too wide");
   if (lk.y && (!dx || lk.ps < 2 || lk.ps > 3)) throw std::runtime_error("xent_linear_bwd: BN link needs dX");
   if (!(eps >= 0.f && eps <= 1.f)) throw std::runtime_error("xent_linear_bwd: label smoothing in [0, 1]");
   const int nbx = dx ? ((I + 15) / 16) * xent_lin_chunks(B) : 0;
   const int nbw = (I + 15) / 16;
   if ((tgt_b != nullptr) != (lam != nullptr)) throw std::runtime_error("xent_linear_bwd: tgt_b and lam go together");
+  if (!bce && (thr || sum_classes))
+    throw std::runtime_error("xent_linear_bwd: target threshold and sum_classes belong to the BCE mode");
+  BceArgs ba{0.f, 0, 0};
+  if (bce) ba = bce_args("xent_linear_bwd", eps, thr, sum_classes, tgt_b, lam);
   auto kern = tgt_b ? (eps != 0.f ? xent_linear_bwd_kernel<true, true> : xent_linear_bwd_kernel<false, true>)
                     : (eps != 0.f ? xent_linear_bwd_kernel<true, false> : xent_linear_bwd_kernel<false, false>);
+  if (bce) kern = tgt_b ? xent_linear_bwd_kernel<false, true, true> : xent_linear_bwd_kernel<false, false, true>;
   hipLaunchKernelGGL(kern, dim3(nbx + nbw + 1), dim3(256), 0, st, logits, tgt, gscale, x, w, B, I, O, dlogits, dx, dw,
-                     db, nbx, nbw, lk, eps, tgt_b, lam);
+                     db, nbx, nbw, lk, eps, tgt_b, lam, ba);
 }
 void avgpool_fwd_launch(const float* x, int N, int HW, int C, float* y, hipStream_t st) {
   if ((long long)N * HW * C >= (1LL << 31)) throw std::runtime_error("avgpool: tensor too large");

@@ -88,6 +88,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("lam") = py::none());
   m.def("xent_bwd", &xent_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("label_smoothing") = 0.0,
         py::arg("target_b") = py::none(), py::arg("lam") = py::none());
+  m.def("bce_fwd", &bce_fwd, py::arg("logits"), py::arg("target"), py::arg("label_smoothing") = 0.0,
+        py::arg("target_threshold") = py::none(), py::arg("sum_classes") = false, py::arg("target_b") = py::none(),
+        py::arg("lam") = py::none(),
+        "binary cross-entropy with logits against the smoothed, mixed, optionally thresholded one-hot rows");
+  m.def("bce_bwd", &bce_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("label_smoothing") = 0.0,
+        py::arg("target_threshold") = py::none(), py::arg("sum_classes") = false, py::arg("target_b") = py::none(),
+        py::arg("lam") = py::none());
   m.def("gemm_log", &gemm_log, py::arg("clear") = false,
         "CDP_GEMM_LOG=1: (kind, M, N, K, bm, bn, splits) of every conv / weight-gradient GEMM launch so far");
   m.def("xent_linear_bwd", &xent_linear_bwd, py::arg("gloss"), py::arg("logits"), py::arg("target"), py::arg("x"),
@@ -95,7 +102,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("db_out") = py::none(), py::arg("link_y") = py::none(), py::arg("link_stats") = py::none(),
         py::arg("link_pool") = false, py::arg("link_relu") = false, py::arg("link_ps") = 2,
         py::arg("label_smoothing") = 0.0, py::arg("target_b") = py::none(), py::arg("lam") = py::none(),
-        "CrossEntropy backward + narrow Linear backward in one launch (+ the BN backward partials of the block "
+        py::arg("bce") = false, py::arg("target_threshold") = py::none(), py::arg("sum_classes") = false,
+        "CrossEntropy (bce: binary cross-entropy) backward + narrow Linear backward in one launch (+ the BN backward partials of the block "
         "that produced the Linear's input, link_*): {dlogits, dx, dw, db, part}");
   py::class_<LarsStep>(m, "LarsStep", "the LARS block of sgd_step / sgd_step_prep (default: off)")
       .def(py::init([](c10::optional<at::Tensor> desc, c10::optional<at::Tensor> meta, c10::optional<at::Tensor> part,

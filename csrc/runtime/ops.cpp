@@ -1877,6 +1877,67 @@ at::Tensor xent_bwd(const at::Tensor& gloss, const at::Tensor& logits_, const at
   return d;
 }
 
+// ---------------------------------------------------------------- binary cross entropy
+// Every logit against its entry of the dense target that (target, target_b, lam, label_smoothing) define
+// (kernels.h bce_fwd_launch), thresholded at target_threshold when given; mean over B * C, or over B with
+// sum_classes. The dense target is never in memory.
+namespace {
+struct BceKnobs {
+  float thr = 0.f;
+  const float* thrp = nullptr;
+};
+BceKnobs bce_knobs(double label_smoothing, const c10::optional<double>& target_threshold, const char* op) {
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, op, ": label_smoothing must be in [0, 1], got ",
+              label_smoothing);
+  BceKnobs k;
+  if (target_threshold.has_value()) {
+    TORCH_CHECK(*target_threshold >= 0.0 && *target_threshold < 1.0, op, ": target_threshold must be in [0, 1), got ",
+                *target_threshold);
+    k.thr = (float)*target_threshold;
+  }
+  return k;
+}
+}  // namespace
+
+at::Tensor bce_fwd(const at::Tensor& logits_, const at::Tensor& target, double label_smoothing,
+                   const c10::optional<double>& target_threshold, bool sum_classes,
+                   const c10::optional<at::Tensor>& target_b, const c10::optional<at::Tensor>& lam) {
+  check_f32_cuda(logits_, "logits");
+  BceKnobs kn = bce_knobs(label_smoothing, target_threshold, "bce_fwd");
+  TORCH_CHECK(logits_.dim() == 2, "bce_fwd: logits must be [B, C]");
+  const at::Tensor logits = logits_.contiguous();
+  const int B = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.numel() == B && target.device() == logits.device(),
+              "bce_fwd: target must be int64, one per row, on the logits' device");
+  const at::Tensor tgt = target.contiguous();
+  const MixPair mp = mix_pair(target_b, lam, logits, "bce_fwd");
+  at::Tensor loss = at::empty({}, logits.options());
+  bce_fwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(tgt.data_ptr<int64_t>()), B, C,
+                 loss.data_ptr<float>(), cur_stream(), (float)label_smoothing,
+                 target_threshold.has_value() ? &kn.thr : nullptr, sum_classes, mp.tbp, mp.lamp);
+  return loss;
+}
+
+at::Tensor bce_bwd(const at::Tensor& gloss, const at::Tensor& logits_, const at::Tensor& target,
+                   double label_smoothing, const c10::optional<double>& target_threshold, bool sum_classes,
+                   const c10::optional<at::Tensor>& target_b, const c10::optional<at::Tensor>& lam) {
+  check_f32_cuda(logits_, "logits");
+  BceKnobs kn = bce_knobs(label_smoothing, target_threshold, "bce_bwd");
+  TORCH_CHECK(logits_.dim() == 2, "bce_bwd: logits must be [B, C]");
+  const at::Tensor logits = logits_.contiguous();
+  const at::Tensor g = gloss.to(at::kFloat).contiguous();
+  const int B = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.numel() == B && target.device() == logits.device(),
+              "bce_bwd: target must be int64, one per row, on the logits' device");
+  const at::Tensor tgt = target.contiguous();
+  const MixPair mp = mix_pair(target_b, lam, logits, "bce_bwd");
+  at::Tensor d = at::empty_like(logits);
+  bce_bwd_launch(logits.data_ptr<float>(), reinterpret_cast<const long long*>(tgt.data_ptr<int64_t>()),
+                 g.data_ptr<float>(), B, C, d.data_ptr<float>(), cur_stream(), (float)label_smoothing,
+                 target_threshold.has_value() ? &kn.thr : nullptr, sum_classes, mp.tbp, mp.lamp);
+  return d;
+}
+
 // {dlogits, dx, dw, db}: the softmax cross-entropy gradient and, in the same launch, the narrow
 // Linear's three gradients from it (ops/functional.py fuses them when the loss directly consumes
 // the classifier's logits)
@@ -1887,9 +1948,14 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
                                         const c10::optional<at::Tensor>& link_stats, bool link_pool, bool link_relu,
                                         int64_t link_ps, double label_smoothing,
                                         const c10::optional<at::Tensor>& target_b,
-                                        const c10::optional<at::Tensor>& lam) {
+                                        const c10::optional<at::Tensor>& lam, bool bce,
+                                        const c10::optional<double>& target_threshold, bool sum_classes) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0,
               "xent_linear_bwd: label_smoothing must be in [0, 1], got ", label_smoothing);
+  TORCH_CHECK(bce || (!target_threshold.has_value() && !sum_classes),
+              "xent_linear_bwd: target_threshold and sum_classes belong to bce=True");
+  BceKnobs kn;
+  if (bce) kn = bce_knobs(label_smoothing, target_threshold, "xent_linear_bwd");
   const at::Tensor logits = logits_.contiguous(), x = x_.contiguous(), w = w_.contiguous();
   const at::Tensor g = gloss.to(at::kFloat).contiguous();
   const at::Tensor tgt = target.contiguous();
@@ -1927,7 +1993,7 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
                          g.data_ptr<float>(), x.data_ptr<float>(), w.data_ptr<float>(), B, I, O, dl.data_ptr<float>(),
                          need_dx ? dx.data_ptr<float>() : nullptr, dw.data_ptr<float>(),
                          has_bias ? db.data_ptr<float>() : nullptr, lk, cur_stream(), (float)label_smoothing, mp.tbp,
-                         mp.lamp);
+                         mp.lamp, bce, target_threshold.has_value() ? &kn.thr : nullptr, sum_classes);
   return {dl, dx, dw, db, part};
 }
 

@@ -87,7 +87,19 @@ std::vector<at::Tensor> xent_linear_bwd(const at::Tensor& gloss, const at::Tenso
                                         bool link_pool = false, bool link_relu = false, int64_t link_ps = 2,
                                         double label_smoothing = 0.0,
                                         const c10::optional<at::Tensor>& target_b = c10::nullopt,
-                                        const c10::optional<at::Tensor>& lam = c10::nullopt);
+                                        const c10::optional<at::Tensor>& lam = c10::nullopt, bool bce = false,
+                                        const c10::optional<double>& target_threshold = c10::nullopt,
+                                        bool sum_classes = false);
+// Binary cross-entropy with logits over index and mixed targets (mean over B * C; sum_classes: over B);
+// target_threshold in [0, 1): the dense target is y > target_threshold
+at::Tensor bce_fwd(const at::Tensor& logits, const at::Tensor& target, double label_smoothing = 0.0,
+                   const c10::optional<double>& target_threshold = c10::nullopt, bool sum_classes = false,
+                   const c10::optional<at::Tensor>& target_b = c10::nullopt,
+                   const c10::optional<at::Tensor>& lam = c10::nullopt);
+at::Tensor bce_bwd(const at::Tensor& gloss, const at::Tensor& logits, const at::Tensor& target,
+                   double label_smoothing = 0.0, const c10::optional<double>& target_threshold = c10::nullopt,
+                   bool sum_classes = false, const c10::optional<at::Tensor>& target_b = c10::nullopt,
+                   const c10::optional<at::Tensor>& lam = c10::nullopt);
 // The LARS block of a fused SGD step (csrc/kernels/lars.h): descriptor, meta and partials from
 // lars_plan, the partials filled by lars_norms just before; ratios: one float per parameter.
 // Without a descriptor the step is plain SGD.
