@@ -21,6 +21,7 @@ from .. import _native
 __all__ = [
     "GradSink",
     "conv_bn_act",
+    "drop_path_scales",
     "linear",
     "cross_entropy",
     "binary_cross_entropy",
@@ -168,7 +169,8 @@ def _get_link(t):
 class _ConvBNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, rm, rv, nbt, momentum, eps, training, stride, pad, pool, relu, residual,
-                res_sink=None, dx_sink=None, w_amax=None, w_t=None, bn_link=False, defer_apply=False):
+                res_sink=None, dx_sink=None, w_amax=None, w_t=None, bn_link=False, defer_apply=False,
+                drop_scale=None):
         C = _native.lib()
         # a residual that is a deferred BatchNorm branch (defer_apply below): its raw conv output and
         # stats go to this block's apply pass instead of the (never written) placeholder
@@ -176,7 +178,7 @@ class _ConvBNAct(torch.autograd.Function):
         out, y, stats, xsave, out_amax, x_amax, w_amax, rmask = C.conv_bn_act_fwd(
             x, w, b, gamma, beta, rm, rv, nbt, momentum, eps, training, stride, pad, pool, relu,
             residual if lazy is None else None, _get_amax(x), w_amax,
-            None if lazy is None else lazy[0], None if lazy is None else lazy[1], defer_apply,
+            None if lazy is None else lazy[0], None if lazy is None else lazy[1], defer_apply, drop_scale,
         )
         if defer_apply:  # statistics only: `out` is a shape-only placeholder nothing may read
             out._cdp_deferred_bn = (y, stats, out._version)
@@ -188,7 +190,7 @@ class _ConvBNAct(torch.autograd.Function):
         # a residual block's ReLU routing: its 1-bit-per-channel pass mask (1/16 of out's bytes) when
         # the kernel wrote one, else out itself
         zout = (rmask if rmask is not None else out) if residual is not None else None
-        ctx.save_for_backward(xsave, w, y, stats, zout)  # xsave: x, or x zero-padded to 4k channels
+        ctx.save_for_backward(xsave, w, y, stats, zout, drop_scale)  # xsave: x, or x zero-padded to 4k channels
         _set_amax(out, out_amax)
         # the producer of x handed over its BN (see _BNLink) if this block is its only consumer
         ctx.link_in = _get_link(x) if dx_sink is None else None
@@ -204,7 +206,7 @@ class _ConvBNAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        x, w, y, stats, zout = ctx.saved_tensors
+        x, w, y, stats, zout, drop_scale = ctx.saved_tensors
         stride, pad, pool, relu, training, has_bias, has_res = ctx.cfg
         res_sink, dx_sink = ctx.sinks
         C = _native.lib()
@@ -230,7 +232,7 @@ class _ConvBNAct(torch.autograd.Function):
         dx, dw, db, dgamma, dbeta, dres, prev_part, _ = C.conv_bn_act_bwd(
             gout, x, w, y, stats, stride, pad, pool, relu, nig[0], has_bias, zout, training,
             _slot(wp, nig[1]), _slot(bp, nig[2] and has_bias), _slot(gp, nig[3]), _slot(betap, nig[4]), addend,
-            *ctx.amax, ctx.w_t, part_in, *prev, bp,
+            *ctx.amax, ctx.w_t, part_in, *prev, bp, drop_scale,
         )
         ctx.w_t = None
         if li is not None:
@@ -254,7 +256,7 @@ class _ConvBNAct(torch.autograd.Function):
             dbeta if ctx.needs_input_grad[4] else None,
             None, None, None, None, None, None, None, None, None, None,
             dres if has_res else None,
-            None, None, None, None, None, None,
+            None, None, None, None, None, None, None,
         )
 
 
@@ -275,7 +277,7 @@ def _bwd_fuse_on() -> bool:
 
 
 def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=None, res_sink=None, dx_sink=None,
-                w_amax=None, w_t=None, bn_link: bool = False, defer_apply: bool = False):
+                w_amax=None, w_t=None, bn_link: bool = False, defer_apply: bool = False, drop_scale=None):
     """``[maxpool2x2](act(bn(conv(x)) [+ residual]))`` for an ``nn.Conv2d`` / ``nn.BatchNorm2d`` pair.
 
     ``pool`` is the reference's ``MaxPool2d(kernel_size=2, stride=2)``; ``relu`` its
@@ -290,7 +292,13 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
     statistics only and return a shape-only placeholder, to be passed as the ``residual`` of exactly
     one ``conv_bn_act``, which then applies this BatchNorm inside its own apply pass (a ResNet
     downsample branch: its normalized output is never written or read back).
+    ``drop_scale`` (stochastic depth; needs ``residual``, no ``pool`` / ``defer_apply``): fp32 ``[N]``, image
+    ``b``'s BatchNorm output is multiplied by ``drop_scale[b]`` before the residual add, inside the same apply
+    pass; the BatchNorm statistics and the residual are untouched. It gets no gradient.
     """
+    if drop_scale is not None and (residual is None or pool or defer_apply):
+        raise ValueError("conv_bn_act: drop_scale scales the branch of a residual block: it needs a residual and "
+                         "takes neither pool nor defer_apply")
     stride = conv.stride[0]
     pad = conv.padding[0]
     if use_native(x):
@@ -319,9 +327,12 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
             w_t if w_t is not None else getattr(conv, "_cdp_wt", None),
             bn_link,
             defer_apply,
+            drop_scale,
         )
     y = F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding)
     y = bn(y)
+    if drop_scale is not None:
+        y = y * drop_scale.to(y.dtype).view(-1, 1, 1, 1)
     if residual is not None:
         y = y + residual
     if relu:
@@ -329,6 +340,47 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
     if pool:
         y = F.max_pool2d(y, 2, 2)
     return y
+
+
+# --------------------------------------------------------------------------- stochastic depth
+_U64 = (1 << 64) - 1
+
+
+def _mix_hash(x):
+    """splitmix64 (csrc/kernels/mix.h) on a numpy uint64 array, wrapping like the device's arithmetic."""
+    import numpy as np
+
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def drop_path_scales(seed: int, counter: int, rates, B: int) -> torch.Tensor:
+    """The stochastic-depth scales of one step: float32 ``[len(rates), B]``, entry ``(i, b)`` 0 when image
+    ``b`` drops block ``i``'s branch, else ``1 / (1 - rates[i])``.
+
+    The host twin of ``drop_path_draw`` (csrc/kernels/drop_path.h), bit for bit: splitmix64 keyed by
+    ``(seed, counter, block)`` under drop path's own stream tag and walked by the image index, a uniform
+    from the hash's top 23 bits, dropped when ``u < p`` in float32, a kept image scaled by
+    ``float32(1) / (float32(1) - p)``. 64-bit integer arithmetic and numpy float32 only, so it is a pure
+    function of its arguments on any host."""
+    import numpy as np
+
+    p = np.asarray([float(r) for r in rates], dtype=np.float32).reshape(-1, 1)
+    nb = p.shape[0]
+    u64 = lambda v: np.asarray([int(v) & _U64], dtype=np.uint64)  # noqa: E731
+    with np.errstate(over="ignore"):
+        blocks = np.arange(nb, dtype=np.uint64)
+        inner = _mix_hash(_mix_hash(u64(counter) + np.uint64(0x682D73636C2D3031)) + blocks)
+        key = _mix_hash(_mix_hash(u64(seed) ^ np.uint64(0x64726F702D706174)) ^ inner)  # [nb]
+        # (the device walks the key by a 32-bit draw index: images stay far below 2^32)
+        r = _mix_hash(key.reshape(-1, 1) + np.arange(B, dtype=np.uint64).reshape(1, -1))  # [nb, B]
+    u = ((r >> np.uint64(41)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 8388608.0)
+    keep = np.float32(1.0) / (np.float32(1.0) - p)  # [nb, 1] float32
+    out = np.where(u < p, np.float32(0.0), np.broadcast_to(keep, u.shape)).astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(out).reshape(nb, B))
 
 
 # --------------------------------------------------------------------------- linear

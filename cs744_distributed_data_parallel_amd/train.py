@@ -135,6 +135,13 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 print("[cdp] rank {}: erase of image 0 in iter {} is {}".format(
                     rank, iter_number, "{} x {} at ({}, {})".format(h, w, top, left) if on else "none"),
                     file=sys.stderr)
+            scales = getattr(getattr(model, "module", model), "last_drop_scales", None)
+            if scales is not None and not (data.is_cuda and torch.cuda.is_current_stream_capturing()):
+                # stochastic depth: the branches the window's last forward dropped (stderr, as above)
+                import sys
+
+                print("[cdp] rank {}: drop path in iter {} dropped {} of {} branches".format(
+                    rank, iter_number, int((scales == 0).sum()), scales.numel()), file=sys.stderr)
         if max_iters is not None and iter_number >= max_iters:
             break
         iter_number += 1
@@ -218,7 +225,13 @@ def run(rank, size, epochs, batch_size, args):
     else:
         criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
     eval_criterion = CrossEntropyLoss()
-    model = get_model(args.model).to(device)
+    model_kw = {}
+    if args.model.startswith("resnet"):
+        # stochastic depth and the zero-initialised last BatchNorm live in the model; every rank draws its own
+        # masks (its seed is derived from --seed and the rank)
+        model_kw = dict(drop_path_rate=args.drop_path, drop_path_seed=args.seed * 1000003 + rank,
+                        zero_init_residual=args.zero_init_residual)
+    model = get_model(args.model, **model_kw).to(device)
     sync = None
     strategy = args.strategy
     if strategy == "ddp":
@@ -433,6 +446,11 @@ def parse_args(argv=None):
                    help="the erased box's share of the image area")
     p.add_argument("--erase-ratio", type=float, nargs=2, default=(0.3, 3.3), metavar=("LO", "HI"),
                    help="the erased box's aspect ratio h / w (log-uniform)")
+    p.add_argument("--drop-path", type=float, default=0.0, metavar="FLOAT",
+                   help="stochastic depth of the resnet models: the last residual block drops its branch per image "
+                        "with probability FLOAT, block i of L with FLOAT * i / (L - 1) (0: off)")
+    p.add_argument("--zero-init-residual", action="store_true",
+                   help="resnet models: start every block's last BatchNorm weight at 0")
     p.add_argument("--crop-size", type=int, default=None, metavar="S",
                    help="output side of both loaders (training: with --rrc-scale; default: the stored size)")
     p.add_argument("--center-crop", type=float, default=None, metavar="FRAC",
@@ -458,6 +476,10 @@ def parse_args(argv=None):
         p.error("--bce-target-thresh and --bce-sum-classes need --loss bce")
     if args.bce_target_thresh is not None and not 0.0 <= args.bce_target_thresh < 1.0:
         p.error("--bce-target-thresh must be in [0, 1)")
+    if not args.model.lower().startswith("resnet") and (args.drop_path != 0.0 or args.zero_init_residual):
+        p.error("--drop-path and --zero-init-residual apply to the resnet models only")
+    if not 0.0 <= args.drop_path < 1.0:
+        p.error("--drop-path must be in [0, 1)")
     return args
 
 

@@ -15,6 +15,7 @@
 // All element kernels move float4 along C (C % 4 == 0).
 #include <algorithm>
 #include <cstdlib>
+#include <stdexcept>
 
 #include "act_max.h"
 #include "common.h"
@@ -328,13 +329,17 @@ __global__ __launch_bounds__(256) void bn_fin_act_kernel(const float* __restrict
 // qmode != 0, so a thread's channel quad is fixed: qmode 1 = one quad (C / 4 divides 256), 2 = two
 // alternating quads (C / 4 == 512), 0 = any C, per-element LDS channel maxima), and folds the
 // per-image / per-channel |max| of what it writes into am (act_max.h).
+// DROP (residual blocks, unpooled branch): stochastic depth, z = drop_scale[img] * bn(y) + residual
+// before the ReLU (drop_path.h); the pass mask is taken from that z. Without DROP drop_scale is not read.
+template <bool DROP>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict__ y, const float* __restrict__ stats,
                                                          const float* __restrict__ res, float* __restrict__ out,
                                                          int N, int H, int W, int C, int pool, int relu, int per,
                                                          int qmode, FastDiv fd_C4, FastDiv fd_HWo, ActMaxOut am,
                                                          unsigned char* __restrict__ rmask,
                                                          const float* __restrict__ res_y,
-                                                         const float* __restrict__ res_st, PoolDiv pd) {
+                                                         const float* __restrict__ res_st, PoolDiv pd,
+                                                         const float* __restrict__ drop_scale) {
   __shared__ ActMaxBlock<kMaxActC> sam;
   const int C4 = C >> 2;
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
@@ -372,6 +377,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict
     for (int ib = i0 + tid; ib < i1; ib += 256 * kU, k += kU) {
       float4 yv[kU], rv[kU];
       int pv[kU], cv[kU];
+      float dsv[DROP ? kU : 1];  // the pixel's image's scale
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const int i = min(ib + 256 * u, i1 - 1);  // past the end: reload the last element, unused
@@ -380,12 +386,16 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict
         const long long off = (long long)pv[u] * C + 4 * cv[u];
         yv[u] = ld4(y + off);
         rv[u] = res ? ld4(res + off) : res_y ? ld4(res_y + off) : f4zero();
+        if constexpr (DROP) dsv[u] = drop_scale[fdiv(pv[u], fd_HWo)];
       }
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         if (ib + 256 * u >= i1) break;
         const int c4 = cv[u];
         float4 z = affine_act(yv[u], ld4(scale + 4 * c4), ld4(shift + 4 * c4), false);
+        if constexpr (DROP) {  // (a dropped image: 0 * bn(y) + r is r, bitwise)
+          z.x *= dsv[u]; z.y *= dsv[u]; z.z *= dsv[u]; z.w *= dsv[u];
+        }
         // res_y: the downsample branch's BatchNorm, applied here instead of materialized
         if (res || res_y) {
           const float4 r = res ? rv[u]
@@ -461,12 +471,16 @@ __device__ __forceinline__ float4 mask_f4(unsigned char m) {
 // Block = 256 threads; for C4 <= 256 threads split as ppb pixel lanes x C4 channel quads.
 // POOL is a template parameter: the pooled branch's four pixels per thread need ~130 VGPRs, which
 // the unpooled instantiation (most of ResNet's BN passes) would otherwise carry at half the occupancy.
-template <int PS, bool POOL>
+// DROP (unpooled only): dz is scaled by drop_scale[image of the pixel] (stochastic depth's backward:
+// every statistic is formed from the gradient at the BN output, s * dz); fd_HW divides by H * W.
+template <int PS, bool POOL, bool DROP = false>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ y, const float* __restrict__ gout,
                                                             const float* __restrict__ stats, float* __restrict__ part,
                                                             int N, int H, int W, int C, int relu,
                                                             const float* __restrict__ zout,
-                                                            const unsigned char* __restrict__ rmask, PoolDiv pd) {
+                                                            const unsigned char* __restrict__ rmask, PoolDiv pd,
+                                                            const float* __restrict__ drop_scale, FastDiv fd_HW) {
+  static_assert(!(POOL && DROP), "a residual block has no pool");
   __shared__ float4 red1[256], red2[256], red3[PS == 3 ? 256 : 1];
   constexpr int pool = POOL ? 1 : 0;
   const int C4 = C >> 2;
@@ -495,9 +509,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
           const float4 yv = ld4(y + px * C + 4 * cq);
           const float4 z = rmask ? mask_f4(rmask[px * C4 + cq])
                                  : zout ? ld4(zout + px * C + 4 * cq) : affine_act(yv, sc, sh, relu);
+          float ds = 1.f;
+          if constexpr (DROP) ds = drop_scale[fdiv((int)px, fd_HW)];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float dz = (!relu || F4GET(z, e) > 0.f) ? F4GET(g, e) : 0.f;
+            float dz = (!relu || F4GET(z, e) > 0.f) ? F4GET(g, e) : 0.f;
+            if constexpr (DROP) dz *= ds;
             const float xh = (F4GET(yv, e) - F4GET(mu, e)) * F4GET(is, e);
             if (e == 0) { a1.x += dz; a2.x += dz * xh; a3.x += xh; }
             if (e == 1) { a1.y += dz; a2.y += dz * xh; a3.y += xh; }
@@ -630,8 +647,8 @@ __global__ __launch_bounds__(256) void chan_finalize_kernel(const float* __restr
 // one pixel; for odd H/W under pooling the uncovered border gets dz = 0. Block b walks the
 // contiguous (pooled) pixel range [b * per, (b + 1) * per), per = ceil(npix / gridDim.x), and folds
 // the per-image / per-channel |max| of the dy it writes into am (act_max.h).
-// (POOL: as bn_bwd_reduce_kernel)
-template <bool POOL>
+// (POOL, DROP: as bn_bwd_reduce_kernel; dres gets the unscaled dz, the shortcut's gradient)
+template <bool POOL, bool DROP = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ y, const float* __restrict__ gout,
                                                            const float* __restrict__ stats,
                                                            const float* __restrict__ sums, float* __restrict__ dy,
@@ -639,7 +656,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            int C, int relu, const float* __restrict__ zout,
                                                            float* __restrict__ dres, FastDiv fd_IMG, FastDiv fd_HW,
                                                            ActMaxOut am, const unsigned char* __restrict__ rmask,
-                                                           PoolDiv pd) {
+                                                           PoolDiv pd, const float* __restrict__ drop_scale) {
+  static_assert(!(POOL && DROP), "a residual block has no pool");
   __shared__ float4 red[256];
   __shared__ ActMaxBlock<kMaxActC> sam;
   constexpr int pool = POOL ? 1 : 0;
@@ -711,6 +729,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
           dz.z = (!relu || z.z > 0.f) ? g.z : 0.f;
           dz.w = (!relu || z.w > 0.f) ? g.w : 0.f;
           if (dres) st4(dres + px * C + 4 * cq, dz);
+          if constexpr (DROP) {
+            const float ds = drop_scale[img];
+            dz.x *= ds; dz.y *= ds; dz.z *= ds; dz.w *= ds;
+          }
           emit(px * C + 4 * cq, yv, dz);
         } else {
           int n, ho, wo;
@@ -1102,7 +1124,7 @@ int bn_act_grid(int N, int H, int W, int C, bool pool) {
 
 void bn_act_fwd_launch(const float* y, const float* stats, const float* res, float* out, int N, int H, int W, int C,
                        bool pool, bool relu, hipStream_t st, ActMaxOut am, unsigned char* rmask, const float* res_y,
-                       const float* res_st) {
+                       const float* res_st, const float* drop_scale) {
   const int C4 = C / 4;
   const long long total = (long long)N * out_pixels_per_image(H, W, pool) * C4;
   // contiguous per-block ranges, whole multiples of 256 float4 (and of C4: fixed channel quads)
@@ -1110,19 +1132,24 @@ void bn_act_fwd_launch(const float* y, const float* stats, const float* res, flo
   const long long unit = qmode == 2 ? 512 : 256;
   const long long blocks = bn_act_grid(N, H, W, C, pool);
   const long long per = std::max(unit, ((total + blocks - 1) / blocks + unit - 1) / unit * unit);
-  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(256), 0, st, y, stats, res,
+  if (drop_scale && (pool || !(res || res_y)))
+    throw std::runtime_error("bn_act_fwd: drop_scale is for an unpooled residual block");
+  hipLaunchKernelGGL(drop_scale ? bn_act_fwd_kernel<true> : bn_act_fwd_kernel<false>,
+                     dim3((unsigned)((total + per - 1) / per)), dim3(256), 0, st, y, stats, res,
                      out, N, H, W, C, pool ? 1 : 0, relu ? 1 : 0, (int)per, qmode, make_fastdiv(C4),
                      make_fastdiv(out_pixels_per_image(H, W, pool)), am, pool ? nullptr : rmask, res_y, res_st,
-                     make_pooldiv(W / 2, H / 2));
+                     make_pooldiv(W / 2, H / 2), drop_scale);
 }
 
 void bn_bwd_reduce_launch(const float* y, const float* gout, const float* stats, float* part, int nblocks, int N,
                           int H, int W, int C, bool pool, bool relu, const float* zout, hipStream_t st,
-                          bool with_xsum, const unsigned char* rmask) {
+                          bool with_xsum, const unsigned char* rmask, const float* drop_scale) {
+  if (drop_scale && pool) throw std::runtime_error("bn_bwd_reduce: drop_scale is for an unpooled residual block");
   auto k = with_xsum ? (pool ? bn_bwd_reduce_kernel<3, true> : bn_bwd_reduce_kernel<3, false>)
                      : (pool ? bn_bwd_reduce_kernel<2, true> : bn_bwd_reduce_kernel<2, false>);
+  if (drop_scale) k = with_xsum ? bn_bwd_reduce_kernel<3, false, true> : bn_bwd_reduce_kernel<2, false, true>;
   hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), 0, st, y, gout, stats, part, N, H, W, C, relu ? 1 : 0, zout, rmask,
-                     make_pooldiv(W / 2, H / 2));
+                     make_pooldiv(W / 2, H / 2), drop_scale, make_fastdiv(H * W));
 }
 
 void chan_finalize_launch(const float* part, int nparts, int C, float* out, float* g0, float* g1, bool accumulate,
@@ -1137,10 +1164,14 @@ void chan_finalize_launch(const float* part, int nparts, int C, float* out, floa
 
 void bn_bwd_apply_launch(const float* y, const float* gout, const float* stats, const float* sums, float* dy,
                          float* dbias_part, int nblocks, int N, int H, int W, int C, bool pool, bool relu,
-                         const float* zout, float* dres, hipStream_t st, ActMaxOut am, const unsigned char* rmask) {
-  hipLaunchKernelGGL(pool ? bn_bwd_apply_kernel<true> : bn_bwd_apply_kernel<false>, dim3(nblocks), dim3(256), 0, st,
+                         const float* zout, float* dres, hipStream_t st, ActMaxOut am, const unsigned char* rmask,
+                         const float* drop_scale) {
+  if (drop_scale && pool) throw std::runtime_error("bn_bwd_apply: drop_scale is for an unpooled residual block");
+  auto k = pool ? bn_bwd_apply_kernel<true> : bn_bwd_apply_kernel<false>;
+  if (drop_scale) k = bn_bwd_apply_kernel<false, true>;
+  hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), 0, st,
                      y, gout, stats, sums, dy, dbias_part, N, H, W, C, relu ? 1 : 0, zout, dres, make_fastdiv(out_pixels_per_image(H, W, pool)),
-                     make_fastdiv(H * W), am, rmask, make_pooldiv(W / 2, H / 2));
+                     make_fastdiv(H * W), am, rmask, make_pooldiv(W / 2, H / 2), drop_scale);
 }
 
 }  // namespace cdp

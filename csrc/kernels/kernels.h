@@ -279,19 +279,34 @@ int bn_act_grid(int N, int H, int W, int C, bool pool);
 // at the float4's index (pixel * C/4 + q). The backward reads it instead of the 16x larger output.
 // res_y / res_st: the residual as a raw conv output and its BN stats block, normalized on the fly
 // (res_y * scale + shift, no activation) instead of a materialized `res`
+// drop_scale (residual blocks only, no pool; the three launches below): one fp32 scale per image
+// (stochastic depth, drop_path.h). The forward computes relu(s[img] * bn(y) + residual); the backward
+// forms every BatchNorm quantity from s[img] * dz and stores the unscaled dz to dres. nullptr launches
+// the instantiations without a scale.
 void bn_act_fwd_launch(const float* y, const float* stats, const float* res, float* out, int N, int H, int W, int C,
                        bool pool, bool relu, hipStream_t st, ActMaxOut am = ActMaxOut{nullptr, nullptr},
-                       unsigned char* rmask = nullptr, const float* res_y = nullptr, const float* res_st = nullptr);
+                       unsigned char* rmask = nullptr, const float* res_y = nullptr, const float* res_st = nullptr,
+                       const float* drop_scale = nullptr);
 void bn_bwd_reduce_launch(const float* y, const float* gout, const float* stats, float* part, int nblocks, int N,
                           int H, int W, int C, bool pool, bool relu, const float* zout, hipStream_t st,
-                          bool with_xsum = false, const unsigned char* rmask = nullptr);
+                          bool with_xsum = false, const unsigned char* rmask = nullptr,
+                          const float* drop_scale = nullptr);
 void chan_finalize_launch(const float* part, int nparts, int C, float* out, float* g0, float* g1, bool accumulate,
                           hipStream_t st, int ps = 2, float* gdb = nullptr, const float* scale = nullptr,
                           long long M = 0, int dbmode = 0);
 void bn_bwd_apply_launch(const float* y, const float* gout, const float* stats, const float* sums, float* dy,
                          float* dbias_part, int nblocks, int N, int H, int W, int C, bool pool, bool relu,
                          const float* zout, float* dres, hipStream_t st, ActMaxOut am = ActMaxOut{nullptr, nullptr},
-                         const unsigned char* rmask = nullptr);
+                         const unsigned char* rmask = nullptr, const float* drop_scale = nullptr);
+
+// drop_path.hip (stochastic depth, drop_path.h)
+// out[nb][B] = the scales of step counter[0] (block i at rate rates[i], both on the device), then
+// counter[0] += 1: one single-workgroup launch per training forward
+void drop_path_draw_launch(long long* counter, unsigned long long seed, const float* rates, int nb, int B, float* out,
+                           hipStream_t st);
+// out[n][nb][B] = the tables of step counters first .. first + n - 1; no counter is read or moved
+void drop_path_table_launch(unsigned long long seed, long long first, long long n, const float* rates, int nb, int B,
+                            float* out, hipStream_t st);
 
 // misc.hip
 // eps: label smoothing in [0, 1] (target distribution (1 - eps) onehot + eps / C; 0: the plain kernels'

@@ -56,9 +56,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("momentum"), py::arg("eps"), py::arg("training"), py::arg("stride"), py::arg("pad"), py::arg("pool"),
         py::arg("relu"), py::arg("residual"), py::arg("x_amax") = py::none(), py::arg("w_amax") = py::none(),
         py::arg("res_y") = py::none(), py::arg("res_stats") = py::none(), py::arg("defer_apply") = false,
+        py::arg("drop_scale") = py::none(),
         "fused conv + BN [+ residual] [+ ReLU] [+ 2x2 max-pool] forward; returns (out, y, stats, x_saved, out_amax, "
         "x_amax, w_amax, relu_mask). defer_apply: statistics only, out a shape-only placeholder; res_y / res_stats: "
-        "the residual as such a deferred branch's raw output and stats, normalized inside this block's apply pass");
+        "the residual as such a deferred branch's raw output and stats, normalized inside this block's apply pass; "
+        "drop_scale (residual blocks): fp32 [N], the BN output of image b is multiplied by drop_scale[b] before the add");
   m.def("act_max", &act_max_of, py::arg("t"),
         "f16x2 engine: an activation's per-image / per-channel |max| slots by the standalone pass (int32 [N + "
         "copies * C], float bits; undefined tensor for other engines)");
@@ -71,7 +73,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dx_addend") = py::none(), py::arg("x_amax") = py::none(), py::arg("w_amax") = py::none(),
         py::arg("w_t") = py::none(), py::arg("part_in") = py::none(), py::arg("prev_y") = py::none(),
         py::arg("prev_stats") = py::none(), py::arg("prev_pool") = false, py::arg("prev_relu") = false,
-        py::arg("prev_ps") = 2, py::arg("bias") = py::none(),
+        py::arg("prev_ps") = 2, py::arg("bias") = py::none(), py::arg("drop_scale") = py::none(),
         "fused block backward; returns (dx, dw, db, dgamma, dbeta, dres, prev_part, dy_amax). prev_* describe the BN whose "
         "output is x: its statistics reduction is then fused into this block's data-gradient reduction and returned "
         "as prev_part (undefined when not fused), which that block's backward takes as part_in");
@@ -224,6 +226,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("erase_noise", &erase_noise, py::arg("seed"), py::arg("counter"), py::arg("B"), py::arg("H"), py::arg("W"),
         "float32 [B, 3, H, W] channels_last: the N(0, 1) fill noise of the erase modes rand and pixel at one "
         "step counter");
+  m.def("drop_path_draw", &drop_path_draw, py::arg("counter"), py::arg("seed"), py::arg("rates"), py::arg("B"),
+        "float32 [nb, B]: the stochastic-depth scales (0 or 1 / (1 - rates[i])) of step counter[0] for nb blocks and "
+        "B images, in one launch that then advances the device int64 counter by one");
+  m.def("drop_path_table", &drop_path_table, py::arg("seed"), py::arg("first"), py::arg("n"), py::arg("rates"),
+        py::arg("B"),
+        "float32 [n, nb, B]: the tables drop_path_draw writes at step counters first .. first + n - 1 (no counter moves)");
   m.def("counter_inc", &counter_inc);
   m.def("stack_mean", &stack_mean);
   m.def("scale_", &scale_);

@@ -1401,6 +1401,15 @@ static bool bn_fin_forced(bool bwd = false) {
   return e && e[0] == '1';
 }
 
+// a block's stochastic-depth scales: fp32 [N] on x's device, N = x's batch (nullptr when not given)
+static const float* drop_scale_ptr(const c10::optional<at::Tensor>& ds, const at::Tensor& x, const char* op) {
+  if (!ds.has_value() || !ds->defined()) return nullptr;
+  TORCH_CHECK(ds->is_cuda() && ds->device() == x.device() && ds->scalar_type() == at::kFloat && ds->dim() == 1 &&
+                  ds->size(0) == x.size(0) && ds->is_contiguous(),
+              op, ": drop_scale must be a contiguous float32 [N] tensor on the input's device");
+  return ds->data_ptr<float>();
+}
+
 std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b,
                                         const c10::optional<at::Tensor>& gamma,
                                         const c10::optional<at::Tensor>& beta,
@@ -1412,10 +1421,16 @@ std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w
                                         const c10::optional<at::Tensor>& x_amax,
                                         const c10::optional<at::Tensor>& w_amax,
                                         const c10::optional<at::Tensor>& res_y,
-                                        const c10::optional<at::Tensor>& res_stats, bool defer_apply) {
+                                        const c10::optional<at::Tensor>& res_stats, bool defer_apply,
+                                        const c10::optional<at::Tensor>& drop_scale) {
+  const bool lazy_res = res_y.has_value() && res_y->defined();
+  // stochastic depth: one scale per image on the BatchNorm output of a residual block (drop_path.h)
+  const float* dsp = drop_scale_ptr(drop_scale, x, "conv_bn_act_fwd");
+  TORCH_CHECK(!dsp || (((residual.has_value() && residual->defined()) || lazy_res) && !pool && !defer_apply),
+              "conv_bn_act_fwd: drop_scale scales the branch of a residual block: it needs a residual and takes "
+              "neither pool nor defer_apply");
   // RGB stem (3x3 / stride 1 / pad 1, Cin <= 4, training BN): one exact-fp32 MFMA kernel reading
   // the raw NHWC input, no channel padding, no operand scales (stem.hip)
-  const bool lazy_res = res_y.has_value() && res_y->defined();
   if (stem_enabled() && stem_ok((int)x.size(1), (int)w.size(2), (int)w.size(3), stride, pad, (int)w.size(0)) &&
       training && !(residual.has_value() && residual->defined()) && !lazy_res && !defer_apply)
     return stem_bn_act_fwd(x, w, b, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, pool,
@@ -1513,7 +1528,7 @@ std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w
     bn_act_fwd_launch(y.data_ptr<float>(), stats.data_ptr<float>(), res.defined() ? res.data_ptr<float>() : nullptr,
                       out.data_ptr<float>(), N, H, W, C, pool, relu, st, am,
                       rmask.defined() ? rmask.data_ptr<uint8_t>() : nullptr, ry.defined() ? ry.data_ptr<float>() : nullptr,
-                      rst.defined() ? rst.data_ptr<float>() : nullptr);
+                      rst.defined() ? rst.data_ptr<float>() : nullptr, dsp);
   return {out, y, stats, xin, out_amax, xa, wa, rmask};
 }
 
@@ -1535,8 +1550,15 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout_, const at::Tenso
                                         const c10::optional<at::Tensor>& part_in,
                                         const c10::optional<at::Tensor>& prev_y,
                                         const c10::optional<at::Tensor>& prev_stats, bool prev_pool, bool prev_relu,
-                                        int64_t prev_ps, const c10::optional<at::Tensor>& bias) {
+                                        int64_t prev_ps, const c10::optional<at::Tensor>& bias,
+                                        const c10::optional<at::Tensor>& drop_scale) {
   check_f32_cuda(gout_, "grad_output");
+  // stochastic depth (the forward's drop_scale): the gradient at the BN output is drop_scale[img] * dz;
+  // the shortcut (dres) gets dz itself
+  const float* dsp = drop_scale_ptr(drop_scale, y, "conv_bn_act_bwd");
+  TORCH_CHECK(!dsp || (zout_.has_value() && zout_->defined() && !pool),
+              "conv_bn_act_bwd: drop_scale scales the branch of a residual block: it needs the block's zout and "
+              "takes no pool");
   const at::Tensor gout = nhwc(gout_);
   const int N = y.size(0), C = y.size(1), H = y.size(2), W = y.size(3);
   auto opts = y.options();
@@ -1577,7 +1599,7 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout_, const at::Tenso
   } else {
     part = at::empty({nblk, C, ps}, opts);
     bn_bwd_reduce_launch(y.data_ptr<float>(), gout.data_ptr<float>(), stats.data_ptr<float>(),
-                         part.data_ptr<float>(), nblk, N, H, W, C, pool, relu, zout_f, st, ps == 3, rmask);
+                         part.data_ptr<float>(), nblk, N, H, W, C, pool, relu, zout_f, st, ps == 3, rmask, dsp);
   }
   const int nparts = (int)part.size(0);
   at::Tensor sums = at::empty({2, C}, opts);
@@ -1643,7 +1665,7 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout_, const at::Tenso
     bn_bwd_apply_launch(y.data_ptr<float>(), gout.data_ptr<float>(), stats.data_ptr<float>(),
                         sums.data_ptr<float>(), dy.data_ptr<float>(), sep_db ? dbpart.data_ptr<float>() : nullptr,
                         nblk, N, H, W, C, pool, relu, zout_f,
-                        dres.defined() ? dres.data_ptr<float>() : nullptr, st, am, rmask);
+                        dres.defined() ? dres.data_ptr<float>() : nullptr, st, am, rmask, dsp);
   const c10::optional<at::Tensor> dya = dy_amax.defined() ? c10::optional<at::Tensor>(dy_amax) : c10::nullopt;
   if (sep_db)
     chan_finalize_launch(dbpart.data_ptr<float>(), nblk, C, nullptr, db.data_ptr<float>(), nullptr, false, st);
@@ -2807,6 +2829,36 @@ at::Tensor erase_noise(int64_t seed, int64_t counter, int64_t B, int64_t H, int6
   at::Tensor out = at::empty({B, 3, H, W}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA).memory_format(
                                                at::MemoryFormat::ChannelsLast));
   erase_noise_launch((unsigned long long)seed, counter, (int)B, (int)H, (int)W, out.data_ptr<float>(), cur_stream());
+  return out;
+}
+
+// ---------------------------------------------------------------- stochastic depth (drop_path.h)
+static void check_drop_rates(const at::Tensor& rates, int64_t B, const char* op) {
+  TORCH_CHECK(rates.is_cuda() && rates.scalar_type() == at::kFloat && rates.dim() == 1 && rates.is_contiguous(), op,
+              ": rates must be a contiguous float32 [nb] tensor on the device");
+  TORCH_CHECK(B >= 0 && B <= 65535 && rates.size(0) <= 65535, op, ": 0 <= B < 65536 and nb < 65536");
+}
+
+at::Tensor drop_path_draw(at::Tensor counter, int64_t seed, const at::Tensor& rates, int64_t B) {
+  check_drop_rates(rates, B, "drop_path_draw");
+  TORCH_CHECK(counter.is_cuda() && counter.device() == rates.device() && counter.scalar_type() == at::kLong &&
+                  counter.numel() == 1,
+              "drop_path_draw: counter must be a one-element int64 tensor on the rates' device");
+  const int64_t nb = rates.size(0);
+  at::Tensor out = at::empty({nb, B}, rates.options());
+  drop_path_draw_launch(reinterpret_cast<long long*>(counter.data_ptr<int64_t>()), (unsigned long long)seed,
+                        rates.data_ptr<float>(), (int)nb, (int)B, out.data_ptr<float>(), cur_stream());
+  return out;
+}
+
+at::Tensor drop_path_table(int64_t seed, int64_t first, int64_t n, const at::Tensor& rates, int64_t B) {
+  check_drop_rates(rates, B, "drop_path_table");
+  const int64_t nb = rates.size(0);
+  TORCH_CHECK(n >= 0 && n * std::max<int64_t>(nb * B, 1) < (int64_t(1) << 31) - 256,
+              "drop_path_table: n >= 0 and n * nb * B < 2^31");
+  at::Tensor out = at::empty({n, nb, B}, rates.options());
+  drop_path_table_launch((unsigned long long)seed, first, n, rates.data_ptr<float>(), (int)nb, (int)B,
+                         out.data_ptr<float>(), cur_stream());
   return out;
 }
 

@@ -43,7 +43,8 @@ std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w
                                         const c10::optional<at::Tensor>& w_amax = c10::nullopt,
                                         const c10::optional<at::Tensor>& res_y = c10::nullopt,
                                         const c10::optional<at::Tensor>& res_stats = c10::nullopt,
-                                        bool defer_apply = false);
+                                        bool defer_apply = false,
+                                        const c10::optional<at::Tensor>& drop_scale = c10::nullopt);
 at::Tensor act_max_of(const at::Tensor& t);
 int64_t act_max_memsets();
 int64_t act_max_copies();
@@ -66,7 +67,8 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout, const at::Tensor
                                         const c10::optional<at::Tensor>& prev_y = c10::nullopt,
                                         const c10::optional<at::Tensor>& prev_stats = c10::nullopt,
                                         bool prev_pool = false, bool prev_relu = false, int64_t prev_ps = 2,
-                                        const c10::optional<at::Tensor>& bias = c10::nullopt);
+                                        const c10::optional<at::Tensor>& bias = c10::nullopt,
+                                        const c10::optional<at::Tensor>& drop_scale = c10::nullopt);
 at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b);
 std::vector<at::Tensor> linear_bwd(const at::Tensor& gy, const at::Tensor& x, const at::Tensor& w, bool need_dx,
                                    bool has_bias, const c10::optional<at::Tensor>& dw_out,
@@ -226,6 +228,11 @@ at::Tensor erase_params(int64_t seed, int64_t first_counter, int64_t n, int64_t 
                         std::vector<double> scale, std::vector<double> ratio, int64_t H, int64_t W);
 // float32 [B, 3, H, W] channels_last: the N(0, 1) fill noise of the erase modes rand and pixel at one counter
 at::Tensor erase_noise(int64_t seed, int64_t counter, int64_t B, int64_t H, int64_t W);
+// Stochastic depth (drop_path.h). rates: device fp32 [nb], one drop probability in [0, 1) per block.
+// float32 [nb, B]: the scales of step counter[0] (a device int64 tensor), which the launch then advances by one
+at::Tensor drop_path_draw(at::Tensor counter, int64_t seed, const at::Tensor& rates, int64_t B);
+// float32 [n, nb, B]: the tables drop_path_draw writes at step counters first .. first + n - 1
+at::Tensor drop_path_table(int64_t seed, int64_t first, int64_t n, const at::Tensor& rates, int64_t B);
 void counter_inc(at::Tensor c);
 void stack_mean(const std::vector<at::Tensor>& srcs, at::Tensor dst);
 void gpu_sleep(double us);
