@@ -24,7 +24,7 @@ OUTPUT = os.path.join(PKG_DIR, "_C" + EXT_SUFFIX)
 
 KERNELS = ["conv_igemm.hip", "conv_x3.hip", "wgrad.hip", "bn.hip", "misc.hip", "stem.hip", "bwd_fuse.hip", "bwd_pair.hip",
            "bwd_pair_d128x128.hip", "bwd_pair_d128x64.hip", "bwd_pair_d64x128.hip", "bwd_pair_d64x64.hip",
-           "grad_norm.hip", "lars.hip", "adam.hip", "drop_path.hip"]
+           "grad_norm.hip", "lars.hip", "adam.hip", "drop_path.hip", "randaug.hip"]
 RUNTIME = ["ops.cpp", "rccl_comm.cpp", "reducer.cpp", "torch_ops.cpp", "bindings.cpp"]
 
 

@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from . import _native
+from . import randaug as _ra
+from .randaug import RANDAUG_OPS, randaug_reference
 
 CIFAR_MEAN = [x / 255.0 for x in [125.3, 123.0, 113.9]]
 CIFAR_STD = [x / 255.0 for x in [63.0, 62.1, 66.7]]
@@ -204,6 +206,24 @@ class DeviceLoader:
     that was not erased); ``erase_schedule`` and ``erase_noise`` give the boxes and the noise of any step.
     ``train=False`` ignores the erase arguments. With ``erase_prob=0`` the loader is exactly what it is
     without them, and ``last_erase`` is None.
+
+    ``randaug_num_ops`` > 0 (and ``train=True``; 3-channel images) turns on RandAugment (Cubuk et al.): every
+    image gets that many operations, drawn uniformly with replacement from ``randaug_ops`` (names out of
+    :data:`RANDAUG_OPS`; default: all 14), each with a random sign where it has one and a level
+    ``L = clamp(randaug_magnitude + randaug_mstd * n, 0, 30)``, ``n ~ N(0, 1)`` per operation (torchvision's 31
+    magnitude bins made continuous; ``mstd`` is timm's). They are applied in sequence to the uint8 image
+    **between the crop / resize / flip and the normalisation** (torchvision's and timm's position), in one
+    launch of their own that stages the batch as uint8 ``[B, OH, OW, 3]``; the loader's usual launch then
+    normalises, erases and mixes the staged batch, so erasing and mixing compose with no change to their draws
+    and the mix partner of an image shows the partner's own operations. All pixel arithmetic is integer
+    arithmetic on the published rows (``last_randaug``, int32 ``[B, num_ops, 8]``:
+    ``{op | sign << 8, level_q = round(256 L), p0 .. p5}``), so :func:`randaug_reference` reproduces
+    ``last_randaug_images`` (the uint8 batch the normalising launch reads: a view of the staging buffer, valid
+    until the next batch) bitwise. With the resize on, the bilinear blend is then exact in integers and
+    re-quantised to uint8 (the PIL order), unlike the RandAugment-off resize. The geometric ops are
+    nearest-neighbour and fill with ``randaug_fill`` (three ints in 0 .. 255; default ``round(255 * mean)``).
+    ``randaug_schedule`` gives the rows of any step. ``train=False`` ignores these arguments. With
+    ``randaug_num_ops=0`` the loader is exactly what it is without them, and ``last_randaug`` is None.
     """
 
     def __init__(self, dataset: ImageDataset, batch_size: int, sampler=None, shuffle: bool = False,
@@ -211,7 +231,8 @@ class DeviceLoader:
                  cutmix_alpha: float = 0.0, mix_prob: float = 1.0, mix_switch_prob: float = 0.5,
                  out_size=None, rrc_scale=None, rrc_ratio=(3.0 / 4.0, 4.0 / 3.0), center_crop=None,
                  erase_prob: float = 0.0, erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3),
-                 erase_mode: str = "const", erase_value=0.0):
+                 erase_mode: str = "const", erase_value=0.0, randaug_num_ops: int = 0,
+                 randaug_magnitude: float = 9.0, randaug_mstd: float = 0.0, randaug_ops=None, randaug_fill=None):
         if not (mixup_alpha >= 0.0 and cutmix_alpha >= 0.0):
             raise ValueError(f"mixup_alpha and cutmix_alpha must be >= 0. Got: {mixup_alpha}, {cutmix_alpha}")
         if not (0.0 <= mix_prob <= 1.0 and 0.0 <= mix_switch_prob <= 1.0):
@@ -256,6 +277,32 @@ class DeviceLoader:
         self.erase_prob, self.erase_scale, self.erase_ratio = float(erase_prob), erase_scale, erase_ratio
         self.erase_mode, self.erase_value = erase_mode, value
         self.last_erase = None
+        if not (isinstance(randaug_num_ops, int) and 0 <= randaug_num_ops <= _ra.MAX_OPS):
+            raise ValueError(f"randaug_num_ops must be an int in 0 .. {_ra.MAX_OPS}. Got: {randaug_num_ops}")
+        if not (0.0 <= float(randaug_magnitude) <= 30.0):
+            raise ValueError(f"randaug_magnitude must be in [0, 30]. Got: {randaug_magnitude}")
+        if not (0.0 <= float(randaug_mstd) < math.inf):
+            raise ValueError(f"randaug_mstd must be >= 0. Got: {randaug_mstd}")
+        names = RANDAUG_OPS if randaug_ops is None else ((randaug_ops,) if isinstance(randaug_ops, str)
+                                                         else tuple(randaug_ops))
+        if not (1 <= len(names) <= _ra.MAX_NAMES and all(n in RANDAUG_OPS for n in names)):
+            raise ValueError(f"randaug_ops must be 1 .. {_ra.MAX_NAMES} names out of {RANDAUG_OPS}. Got: {randaug_ops}")
+        if randaug_fill is None:
+            fill = [min(255, max(0, int(round(255.0 * float(dataset.mean[min(c, len(dataset.mean) - 1)])))))
+                    for c in range(3)]
+        else:
+            fill = list(randaug_fill) if isinstance(randaug_fill, (tuple, list)) else None
+            if not (fill is not None and len(fill) == 3
+                    and all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 255 for v in fill)):
+                raise ValueError(f"randaug_fill must be three integers in 0 .. 255. Got: {randaug_fill}")
+        if train and randaug_num_ops > 0 and dataset.images.shape[3] != 3:
+            raise ValueError(f"RandAugment needs 3-channel images. Got: {dataset.images.shape[3]} channels")
+        self.randaug_num_ops, self.randaug_magnitude = randaug_num_ops, float(randaug_magnitude)
+        self.randaug_mstd, self.randaug_ops, self.randaug_fill = float(randaug_mstd), names, fill
+        self._randaug_kinds = [RANDAUG_OPS.index(n) for n in names]
+        self.last_randaug = None
+        self.last_randaug_images = None
+        self._randaug_bufs = {}
         self.ds, self.batch_size, self.sampler, self.shuffle = dataset, batch_size, sampler, shuffle
         self.train, self.drop_last, self.seed = train, drop_last, seed
         self.dev = dataset.images.device
@@ -329,6 +376,52 @@ class DeviceLoader:
         """Whether images are erased (``erase_prob`` > 0 on a training loader)."""
         return self.train and self.erase_prob > 0.0
 
+    @property
+    def randaugmenting(self) -> bool:
+        """Whether images get RandAugment operations (``randaug_num_ops`` > 0 on a training loader)."""
+        return self.train and self.randaug_num_ops > 0
+
+    def _randaug_stage(self, C, idx, offset, bsz, nbatches, pad, flip):
+        """The RandAugment launch: the batch gathered, cropped, flipped and augmented as uint8 in the loader's
+        staging buffers (allocated once per batch shape: a captured step allocates nothing per replay), and its
+        labels. Publishes ``last_randaug``, ``last_randaug_images`` and, with the resize, ``last_crops``."""
+        OH, OW = self.out_size if self.resizing else tuple(self.ds.shape[:2])
+        bufs = self._randaug_bufs.get((bsz, OH, OW))
+        if bufs is None:
+            bufs = (torch.empty(bsz, OH, OW, 3, dtype=torch.uint8, device=self.dev),
+                    torch.empty(bsz, OH, OW, 3, dtype=torch.uint8, device=self.dev),
+                    torch.empty(bsz, dtype=torch.int64, device=self.dev))
+            self._randaug_bufs[(bsz, OH, OW)] = bufs
+        buf_a, buf_b, staged_labels = bufs
+        rows = torch.empty(bsz, self.randaug_num_ops, _ra.ROW, dtype=torch.int32, device=self.dev)
+        crops = torch.empty(bsz, 5, dtype=torch.int32, device=self.dev) if self.resizing else None
+        C.randaug(self.ds.images, idx, offset, bsz, OH, OW, self.resizing, self.rrc_scale or (1.0, 1.0), self.rrc_ratio,
+                  pad, flip, self._counter, self.seed, nbatches, self.ds.labels, staged_labels, crops,
+                  self.randaug_num_ops, self.randaug_magnitude, self.randaug_mstd, self._randaug_kinds,
+                  self.randaug_fill, buf_a, buf_b, rows)
+        self.last_randaug = rows
+        self.last_randaug_images = buf_a if self.randaug_num_ops % 2 == 0 else buf_b
+        if self.resizing:
+            self.last_crops = crops
+        return self.last_randaug_images, staged_labels
+
+    def randaug_schedule(self, first_counter: int, n: int, B: int) -> torch.Tensor:
+        """The RandAugment rows ``{op | sign << 8, level_q, p0 .. p5}`` of the ``B`` images of the batches at step
+        counters ``first_counter .. first_counter + n - 1`` (int32 ``[n, B, num_ops, 8]``; training loaders with
+        ``randaug_num_ops`` > 0)."""
+        if not self.randaugmenting:
+            raise ValueError("randaug_schedule: a training loader with randaug_num_ops > 0 draws operations; this "
+                             "one does not")
+        H, W = self._erase_size()
+        if self.dev.type == "cuda":
+            return _native.lib().randaug_params(self.seed, first_counter, n, B, self.randaug_num_ops,
+                                                self.randaug_magnitude, self.randaug_mstd, self._randaug_kinds,
+                                                self.randaug_fill, H, W)
+        return torch.stack([_ra.randaug_draw(self.seed, first_counter + i, B, self.randaug_num_ops,
+                                             self.randaug_magnitude, self.randaug_mstd, self._randaug_kinds, H, W)
+                            for i in range(n)]) if n else torch.zeros(0, B, self.randaug_num_ops, _ra.ROW,
+                                                                      dtype=torch.int32)
+
     def batch(self, idx: torch.Tensor, offset: int, bsz: int, out: Optional[torch.Tensor] = None,
               nbatches: int = 0):
         """Produce one batch from ``idx[offset:offset+bsz]`` (graph-capturable on GPU).
@@ -351,7 +444,25 @@ class DeviceLoader:
                 self.last_erase = torch.empty(bsz, 5, dtype=torch.int32, device=self.dev)
                 ekw = dict(erase_prob=self.erase_prob, erase_scale=self.erase_scale, erase_ratio=self.erase_ratio,
                            erase_mode=self.erase_mode, erase_value=self.erase_value, erase=self.last_erase)
-            if self.resizing:
+            if self.randaugmenting:
+                # one launch stages the batch as uint8 and applies every image's operations; the plain augment
+                # launch below then normalises, erases and mixes the staged batch (identity indices, no crop, no
+                # flip) with the draws of the same counter
+                if self.resizing and out is not None and tuple(out.shape) != (bsz, 3) + tuple(self.out_size):
+                    raise ValueError(f"DeviceLoader.batch: out has shape {tuple(out.shape)}, the batch is "
+                                     f"{(bsz, 3) + tuple(self.out_size)}")
+                staged, staged_labels = self._randaug_stage(C, idx, offset, bsz, nbatches, pad, flip)
+                mkw = {}
+                if self.mixing:
+                    target_b = torch.empty(bsz, dtype=torch.int64, device=self.dev)
+                    info = torch.empty(8, dtype=torch.float32, device=self.dev)
+                    mkw = dict(mixup_alpha=self.mixup_alpha, cutmix_alpha=self.cutmix_alpha, mix_prob=self.mix_prob,
+                               mix_switch_prob=self.mix_switch_prob, mix=info, labels_b=target_b)
+                data = C.augment(staged, None, 0, bsz, self.ds.mean, self.ds.std, 0, False, self._counter, self.seed,
+                                 out, 0, staged_labels, target, **mkw, **ekw)
+                if self.mixing:
+                    target = MixTarget(target, target_b, info[1:2], info)
+            elif self.resizing:
                 OH, OW = self.out_size
                 if out is not None and tuple(out.shape) != (bsz, self.ds.shape[2], OH, OW):
                     raise ValueError(f"DeviceLoader.batch: out has shape {tuple(out.shape)}, the batch is "
@@ -387,9 +498,18 @@ class DeviceLoader:
             else:
                 self._check_one_batch_per_step()
             return data, target
-        ctr = int(self._counter.item()) if (nbatches > 0 or self.mixing or self.resizing or self.erasing) else None
+        ctr = int(self._counter.item()) if (nbatches > 0 or self.mixing or self.resizing or self.erasing
+                                            or self.randaugmenting) else None
         if nbatches > 0:
             offset += (ctr % nbatches) * bsz
+        if self.randaugmenting:
+            self._counter += 1
+            data, target = self._cpu_randaug_batch(idx[offset : offset + bsz], pad, flip, ctr)
+            if self.erasing:
+                data = self._cpu_erase(data, ctr)
+            if out is not None:
+                data = out.copy_(data)
+            return self._cpu_mix(data, target, ctr) if self.mixing else (data, target)
         if self.resizing:
             self._counter += 1
             data, target = self._cpu_resize_batch(idx[offset : offset + bsz], flip, ctr)
@@ -553,6 +673,42 @@ class DeviceLoader:
         std = torch.tensor(self.ds.std, dtype=torch.float64).view(1, -1, 1, 1)
         out = ((out / 255.0 - mean) / std).float()
         return out.contiguous(memory_format=torch.channels_last), self.ds.labels.index_select(0, sel)
+
+    def _cpu_randaug_batch(self, sel, pad, flip, ctr):
+        """The RandAugment launch's semantics on the host: the batch staged as uint8 (the pad-shift crop and flip
+        of ``_cpu_batch``'s generator, or the window rule of ``_cpu_resize_batch``'s generator with the exact
+        integer bilinear :func:`randaug.stage_resize`), the host evaluation of the device's draw (ops and signs
+        are the device's), :func:`randaug_reference`, then the normalisation."""
+        imgs = self.ds.images.index_select(0, sel)
+        B, H, W, _ = imgs.shape
+        if self.resizing:
+            OH, OW = self.out_size
+            g = torch.Generator().manual_seed((0x727263 << 40) + self.seed * 1000003 + ctr)
+            crops = torch.zeros(B, 5, dtype=torch.int32)
+            for b in range(B):
+                top, left, h, w = self._rrc_get_params(H, W, self.rrc_scale, self.rrc_ratio, g)
+                fl = bool(flip) and float(torch.rand(1, generator=g)) < 0.5
+                crops[b] = torch.tensor([top, left, h, w, int(fl)], dtype=torch.int32)
+            self.last_crops = crops
+            staged = _ra.stage_resize(imgs, crops, OH, OW)
+        else:
+            OH, OW = H, W
+            g = torch.Generator().manual_seed(self.seed * 1000003 + ctr)
+            if pad:
+                oy = (torch.randint(0, 2 * pad + 1, (B,), generator=g) - pad).tolist()
+                ox = (torch.randint(0, 2 * pad + 1, (B,), generator=g) - pad).tolist()
+            else:
+                oy = ox = [0] * B
+            fl = (torch.rand(B, generator=g) < 0.5).tolist() if flip else [False] * B
+            staged = _ra.stage_plain(imgs, oy, ox, fl)
+        rows = _ra.randaug_draw(self.seed, ctr, B, self.randaug_num_ops, self.randaug_magnitude, self.randaug_mstd,
+                                self._randaug_kinds, OH, OW)
+        self.last_randaug = rows
+        self.last_randaug_images = randaug_reference(staged, rows, self.randaug_fill)
+        mean = torch.tensor(self.ds.mean).view(1, -1, 1, 1)
+        std = torch.tensor(self.ds.std).view(1, -1, 1, 1)
+        x = (self.last_randaug_images.permute(0, 3, 1, 2).float().div_(255.0) - mean) / std
+        return x.contiguous(memory_format=torch.channels_last), self.ds.labels.index_select(0, sel)
 
     def _cpu_mix(self, data, target, ctr):
         """The device kernel's semantics on the host: one draw per batch from a generator of its own

@@ -135,6 +135,15 @@ def train_model(model, train_loader, optimizer, criterion, rank=0, sync=None, st
                 print("[cdp] rank {}: erase of image 0 in iter {} is {}".format(
                     rank, iter_number, "{} x {} at ({}, {})".format(h, w, top, left) if on else "none"),
                     file=sys.stderr)
+            ra_rows = getattr(train_loader, "last_randaug", None)
+            if ra_rows is not None and not (data.is_cuda and torch.cuda.is_current_stream_capturing()):
+                # RandAugment: the first image's operations in the window's last batch (stderr, as above)
+                import sys
+
+                from .randaug import describe
+
+                print("[cdp] rank {}: randaug of image 0 in iter {} is {}".format(
+                    rank, iter_number, " ".join(describe(r) for r in ra_rows[0].tolist())), file=sys.stderr)
             scales = getattr(getattr(model, "module", model), "last_drop_scales", None)
             if scales is not None and not (data.is_cuda and torch.cuda.is_current_stream_capturing()):
                 # stochastic depth: the branches the window's last forward dropped (stderr, as above)
@@ -203,7 +212,9 @@ def run(rank, size, epochs, batch_size, args):
                                 out_size=args.crop_size if args.rrc_scale is not None else None,
                                 rrc_scale=args.rrc_scale, rrc_ratio=args.rrc_ratio, erase_prob=args.random_erase,
                                 erase_scale=args.erase_scale, erase_ratio=args.erase_ratio,
-                                erase_mode=args.erase_mode)
+                                erase_mode=args.erase_mode, randaug_num_ops=args.randaug[0],
+                                randaug_magnitude=args.randaug[1], randaug_mstd=args.randaug_mstd,
+                                randaug_ops=args.randaug_ops, randaug_fill=args.randaug_fill)
     print("Size of training set is {}".format(len(train_loader)))
     test_set = build_data(args, device, False)
     test_loader = DeviceLoader(test_set, batch_size, shuffle=False, train=False, out_size=args.crop_size,
@@ -446,6 +457,15 @@ def parse_args(argv=None):
                    help="the erased box's share of the image area")
     p.add_argument("--erase-ratio", type=float, nargs=2, default=(0.3, 3.3), metavar=("LO", "HI"),
                    help="the erased box's aspect ratio h / w (log-uniform)")
+    p.add_argument("--randaug", type=float, nargs=2, default=(0, 9.0), metavar=("N", "M"),
+                   help="RandAugment of the training images: N operations per image at magnitude M in [0, 30], on the "
+                        "uint8 image after crop / resize / flip and before the normalisation (N = 0: off)")
+    p.add_argument("--randaug-mstd", type=float, default=0.0, metavar="S",
+                   help="RandAugment: standard deviation of the per-operation magnitude noise (timm's mstd)")
+    p.add_argument("--randaug-ops", nargs="+", default=None, metavar="NAME",
+                   help="RandAugment: the operations to draw from (default: all 14)")
+    p.add_argument("--randaug-fill", type=int, nargs=3, default=None, metavar=("R", "G", "B"),
+                   help="RandAugment: the geometric operations' value outside the image (default: 255 * mean)")
     p.add_argument("--drop-path", type=float, default=0.0, metavar="FLOAT",
                    help="stochastic depth of the resnet models: the last residual block drops its branch per image "
                         "with probability FLOAT, block i of L with FLOAT * i / (L - 1) (0: off)")
@@ -480,6 +500,11 @@ def parse_args(argv=None):
         p.error("--drop-path and --zero-init-residual apply to the resnet models only")
     if not 0.0 <= args.drop_path < 1.0:
         p.error("--drop-path must be in [0, 1)")
+    if args.randaug[0] != int(args.randaug[0]):
+        p.error("--randaug N M: N is a whole number of operations")
+    args.randaug = (int(args.randaug[0]), float(args.randaug[1]))
+    if args.randaug_fill is not None:
+        args.randaug_fill = tuple(args.randaug_fill)
     return args
 
 

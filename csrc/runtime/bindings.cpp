@@ -226,6 +226,20 @@ PYBIND11_MODULE(_C, m) {
   m.def("erase_noise", &erase_noise, py::arg("seed"), py::arg("counter"), py::arg("B"), py::arg("H"), py::arg("W"),
         "float32 [B, 3, H, W] channels_last: the N(0, 1) fill noise of the erase modes rand and pixel at one "
         "step counter");
+  m.def("randaug", &randaug, py::arg("images"), py::arg("indices"), py::arg("idx_offset"), py::arg("batch"),
+        py::arg("out_h"), py::arg("out_w"), py::arg("resize"), py::arg("scale"), py::arg("ratio"), py::arg("pad"),
+        py::arg("flip"), py::arg("counter"), py::arg("seed"), py::arg("nbatches"), py::arg("labels"),
+        py::arg("labels_out"), py::arg("crops"), py::arg("num_ops"), py::arg("magnitude"), py::arg("mstd"),
+        py::arg("ops"), py::arg("fill"), py::arg("buf_a"), py::arg("buf_b"), py::arg("rows"),
+        "RandAugment: gather + crop (pad-shift, or RandomResizedCrop with an exact integer bilinear resize) + flip one "
+        "batch as uint8 [batch, out_h, out_w, 3] and apply num_ops drawn operations per image in one launch; the "
+        "result is in buf_a for an even num_ops and in buf_b for an odd one; rows (int32 [batch, num_ops, 8]) "
+        "receives {op | sign << 8, level_q, p0 .. p5} per operation");
+  m.def("randaug_params", &randaug_params, py::arg("seed"), py::arg("first_counter"), py::arg("n"), py::arg("B"),
+        py::arg("num_ops"), py::arg("magnitude"), py::arg("mstd"), py::arg("ops"), py::arg("fill"), py::arg("H"),
+        py::arg("W"),
+        "int32 [n, B, num_ops, 8]: the rows randaug publishes at step counters first_counter .. first_counter + n - 1 "
+        "for an H x W staged image");
   m.def("drop_path_draw", &drop_path_draw, py::arg("counter"), py::arg("seed"), py::arg("rates"), py::arg("B"),
         "float32 [nb, B]: the stochastic-depth scales (0 or 1 / (1 - rates[i])) of step counter[0] for nb blocks and "
         "B images, in one launch that then advances the device int64 counter by one");

@@ -28,6 +28,7 @@
 
 #include "../kernels/adam.h"
 #include "../kernels/kernels.h"
+#include "../kernels/randaug.h"
 
 namespace cdp {
 
@@ -2829,6 +2830,119 @@ at::Tensor erase_noise(int64_t seed, int64_t counter, int64_t B, int64_t H, int6
   at::Tensor out = at::empty({B, 3, H, W}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA).memory_format(
                                                at::MemoryFormat::ChannelsLast));
   erase_noise_launch((unsigned long long)seed, counter, (int)B, (int)H, (int)W, out.data_ptr<float>(), cur_stream());
+  return out;
+}
+
+// ---------------------------------------------------------------- RandAugment (randaug.h)
+namespace {
+RandAugCfg randaug_cfg(int64_t num_ops, double magnitude, double mstd, const std::vector<int64_t>& ops,
+                       const std::vector<int64_t>& fill, const char* op) {
+  TORCH_CHECK(num_ops >= 1 && num_ops <= kRaMaxOps, op, ": 1 <= num_ops <= 8 required. Got: ", num_ops);
+  TORCH_CHECK(magnitude >= 0.0 && magnitude <= 30.0, op, ": magnitude must be in [0, 30]. Got: ", magnitude);
+  TORCH_CHECK(mstd >= 0.0 && std::isfinite(mstd), op, ": mstd must be >= 0. Got: ", mstd);
+  TORCH_CHECK(!ops.empty() && ops.size() <= (size_t)kRaMaxNames, op, ": 1 .. 32 ops to draw from required");
+  TORCH_CHECK(fill.size() == 3, op, ": fill is three integers in 0 .. 255");
+  RandAugCfg c;
+  c.num_ops = (int)num_ops;
+  c.magnitude = (float)magnitude;
+  c.mstd = (float)mstd;
+  c.n_names = (int)ops.size();
+  for (size_t i = 0; i < ops.size(); ++i) {
+    TORCH_CHECK(ops[i] >= 0 && ops[i] < kRaNumKinds, op, ": unknown op kind ", ops[i]);
+    c.names[i] = (unsigned char)ops[i];
+  }
+  for (int i = 0; i < 3; ++i) {
+    TORCH_CHECK(fill[i] >= 0 && fill[i] <= 255, op, ": fill is three integers in 0 .. 255");
+    c.fill[i] = (int)fill[i];
+  }
+  return c;
+}
+}  // namespace
+void randaug(const at::Tensor& images, const c10::optional<at::Tensor>& indices, int64_t idx_offset, int64_t batch,
+             int64_t out_h, int64_t out_w, bool resize, std::vector<double> scale, std::vector<double> ratio,
+             int64_t pad, bool flip, const c10::optional<at::Tensor>& counter, int64_t seed, int64_t nbatches,
+             const at::Tensor& labels, at::Tensor labels_out, const c10::optional<at::Tensor>& crops, int64_t num_ops,
+             double magnitude, double mstd, std::vector<int64_t> ops, std::vector<int64_t> fill, at::Tensor buf_a,
+             at::Tensor buf_b, at::Tensor rows) {
+  TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.dim() == 4 && images.is_contiguous(),
+              "randaug: images must be contiguous uint8 [N, H, W, C] on the GPU");
+  const int64_t H = images.size(1), W = images.size(2), C = images.size(3);
+  TORCH_CHECK(C == 3, "randaug: 3-channel images only. Got: ", C);
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 0x7fff && W <= 0x7fff, "randaug: 1 <= H, W < 32768");
+  TORCH_CHECK(out_h >= 1 && out_w >= 1 && out_h <= 0x7fff && out_w <= 0x7fff,
+              "randaug: 1 <= out_h, out_w < 32768. Got: ", out_h, ", ", out_w);
+  TORCH_CHECK(batch >= 1 && batch <= 65535, "randaug: 1 <= batch < 65536");
+  TORCH_CHECK(resize || (out_h == H && out_w == W), "randaug: without the resize the output is H x W");
+  TORCH_CHECK(pad >= 0 && pad <= 0x7fff, "randaug: 0 <= pad < 32768");
+  const RandAugCfg cfg = randaug_cfg(num_ops, magnitude, mstd, ops, fill, "randaug");
+  RaStage s{};
+  s.imgs = images.data_ptr<uint8_t>();
+  s.idx_off = idx_offset;
+  s.B = (int)batch;
+  s.H = (int)H;
+  s.W = (int)W;
+  s.OH = (int)out_h;
+  s.OW = (int)out_w;
+  s.resize = resize ? 1 : 0;
+  s.rc = RrcCfg{1.f, 1.f, 0.f, 0.f};
+  s.pad = resize ? 0 : (int)pad;
+  s.flip = flip ? 1 : 0;
+  s.seed = (unsigned long long)seed;
+  s.nbatches = nbatches;
+  if (resize) {
+    s.rc = rrc_cfg(scale, ratio, "randaug");
+    TORCH_CHECK(crops.has_value() && crops->defined() && crops->is_cuda() && crops->device() == images.device() &&
+                    crops->scalar_type() == at::kInt && crops->is_contiguous() && crops->dim() == 2 &&
+                    crops->size(0) == batch && crops->size(1) == kCropRow,
+                "randaug: the resize needs crops, a contiguous int32 [batch, 5] tensor on the images' device");
+    s.crops = crops->data_ptr<int>();
+  }
+  if (indices.has_value() && indices->defined()) {
+    TORCH_CHECK(indices->device() == images.device() && indices->scalar_type() == at::kLong && indices->is_contiguous(),
+                "randaug: indices must be a contiguous int64 tensor on the images' device");
+    // the kernel reads idx[idx_offset + (counter % nbatches) * batch + b] for b < batch
+    TORCH_CHECK(idx_offset >= 0 && idx_offset + std::max<int64_t>(nbatches, 1) * batch <= indices->numel(),
+                "randaug: idx_offset + max(nbatches, 1) * batch = ", idx_offset + std::max<int64_t>(nbatches, 1) * batch,
+                " exceeds the ", indices->numel(), " indices");
+    s.idx = reinterpret_cast<const long long*>(indices->data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(idx_offset >= 0 && idx_offset + std::max<int64_t>(nbatches, 1) * batch <= images.size(0),
+                "randaug: the batch range exceeds the ", images.size(0), " images");
+  }
+  if (counter.has_value() && counter->defined()) {
+    TORCH_CHECK(counter->device() == images.device() && counter->scalar_type() == at::kLong && counter->numel() >= 1,
+                "randaug: counter must be an int64 tensor on the images' device");
+    s.counter = reinterpret_cast<const long long*>(counter->data_ptr<int64_t>());
+  }
+  TORCH_CHECK(nbatches >= 0 && (nbatches == 0 || s.counter), "randaug: counter-driven batch offsets need the counter");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels_out.scalar_type() == at::kLong &&
+                  labels.device() == images.device() && labels_out.device() == images.device() &&
+                  labels.numel() >= images.size(0) && labels_out.numel() >= batch && labels.is_contiguous() &&
+                  labels_out.is_contiguous(),
+              "randaug: labels (one per image) and labels_out (holding the batch) must be contiguous int64 tensors on "
+              "the images' device");
+  s.labels = reinterpret_cast<const long long*>(labels.data_ptr<int64_t>());
+  s.labels_out = reinterpret_cast<long long*>(labels_out.data_ptr<int64_t>());
+  const int64_t need = batch * out_h * out_w * 3;
+  for (const at::Tensor* t : {&buf_a, &buf_b})
+    TORCH_CHECK(t->is_cuda() && t->device() == images.device() && t->scalar_type() == at::kByte && t->is_contiguous() &&
+                    t->numel() == need,
+                "randaug: buf_a and buf_b must be contiguous uint8 [batch, out_h, out_w, 3] tensors on the images' device");
+  TORCH_CHECK(buf_a.data_ptr() != buf_b.data_ptr(), "randaug: buf_a and buf_b must be two buffers");
+  TORCH_CHECK(rows.is_cuda() && rows.device() == images.device() && rows.scalar_type() == at::kInt &&
+                  rows.is_contiguous() && rows.numel() == batch * num_ops * kRaRow,
+              "randaug: rows must be a contiguous int32 [batch, num_ops, 8] tensor on the images' device");
+  randaug_launch(s, cfg, buf_a.data_ptr<uint8_t>(), buf_b.data_ptr<uint8_t>(), rows.data_ptr<int>(), cur_stream());
+}
+
+at::Tensor randaug_params(int64_t seed, int64_t first_counter, int64_t n, int64_t B, int64_t num_ops, double magnitude,
+                          double mstd, std::vector<int64_t> ops, std::vector<int64_t> fill, int64_t H, int64_t W) {
+  TORCH_CHECK(n >= 0 && B >= 0 && B <= 65535 && H >= 1 && W >= 1 && H <= 0x7fff && W <= 0x7fff,
+              "randaug_params: n >= 0, 0 <= B < 65536, 1 <= H, W < 32768");
+  const RandAugCfg cfg = randaug_cfg(num_ops, magnitude, mstd, ops, fill, "randaug_params");
+  at::Tensor out = at::empty({n, B, num_ops, kRaRow}, at::TensorOptions().dtype(at::kInt).device(at::kCUDA));
+  randaug_params_launch((unsigned long long)seed, first_counter, n, (int)B, cfg, (int)H, (int)W, out.data_ptr<int>(),
+                        cur_stream());
   return out;
 }
 

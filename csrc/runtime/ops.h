@@ -228,6 +228,20 @@ at::Tensor erase_params(int64_t seed, int64_t first_counter, int64_t n, int64_t 
                         std::vector<double> scale, std::vector<double> ratio, int64_t H, int64_t W);
 // float32 [B, 3, H, W] channels_last: the N(0, 1) fill noise of the erase modes rand and pixel at one counter
 at::Tensor erase_noise(int64_t seed, int64_t counter, int64_t B, int64_t H, int64_t W);
+// RandAugment (randaug.h): stage `batch` images as uint8 [batch, out_h, out_w, 3] into buf_a (the gather of augment;
+// resize: RandomResizedCrop with integer bilinear taps, crops receives {top, left, h, w, flip}; otherwise the
+// pad-shift crop) and apply num_ops drawn operations per image ping-pong between buf_a and buf_b: the result is in
+// buf_a for an even num_ops, in buf_b for an odd one. ops: op kinds to draw from; fill: three ints in 0 .. 255;
+// rows: int32 [batch, num_ops, 8], receives the rows. One launch.
+void randaug(const at::Tensor& images, const c10::optional<at::Tensor>& indices, int64_t idx_offset, int64_t batch,
+             int64_t out_h, int64_t out_w, bool resize, std::vector<double> scale, std::vector<double> ratio,
+             int64_t pad, bool flip, const c10::optional<at::Tensor>& counter, int64_t seed, int64_t nbatches,
+             const at::Tensor& labels, at::Tensor labels_out, const c10::optional<at::Tensor>& crops, int64_t num_ops,
+             double magnitude, double mstd, std::vector<int64_t> ops, std::vector<int64_t> fill, at::Tensor buf_a,
+             at::Tensor buf_b, at::Tensor rows);
+// int32 [n, B, num_ops, 8]: the rows randaug publishes at counters first_counter + i for an H x W staged image
+at::Tensor randaug_params(int64_t seed, int64_t first_counter, int64_t n, int64_t B, int64_t num_ops, double magnitude,
+                          double mstd, std::vector<int64_t> ops, std::vector<int64_t> fill, int64_t H, int64_t W);
 // Stochastic depth (drop_path.h). rates: device fp32 [nb], one drop probability in [0, 1) per block.
 // float32 [nb, B]: the scales of step counter[0] (a device int64 tensor), which the launch then advances by one
 at::Tensor drop_path_draw(at::Tensor counter, int64_t seed, const at::Tensor& rates, int64_t B);
