@@ -25,6 +25,21 @@
 namespace cdp {
 namespace {
 
+// momentum=None (cumulative average, momentum < 0): every channel's factor is 1 / (k + 1) with k the
+// count from before this launch, and the launch advances the count once. A plain read of nbt[0]
+// beside another workgroup's nbt[0] += 1 is not ordered: a workgroup scheduled after that one had
+// finished read k + 1. Instead each of the C channel threads adds one arrival to the counter's
+// high bits in the same atomic that returns the count in its low bits, so all of them read k; the
+// last to arrive takes the C arrivals out again and adds the step. No launch, no second buffer,
+// nothing for the host to wait for. (Counts stay below 2^40, channels below 2^23.)
+__device__ __forceinline__ long long cma_arrive(long long* nbt, int C) {
+  constexpr int SH = 40;
+  unsigned long long* p = reinterpret_cast<unsigned long long*>(nbt);
+  const unsigned long long old = atomicAdd(p, 1ull << SH);
+  if ((int)(old >> SH) == C - 1) atomicAdd(p, 1ull - ((unsigned long long)C << SH));
+  return (long long)(old & ((1ull << SH) - 1));
+}
+
 // ------------------------------------------------------------------ finalize (train)
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int nparts, int rpp, int M,
                                                           int C, const float* __restrict__ gamma,
@@ -91,14 +106,15 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     stats[C + c] = invstd;
     stats[2 * C + c] = scale;
     stats[3 * C + c] = bb - (float)mean * scale;
+    const bool cma = momentum < 0.f && running_mean && nbt;  // (cma_arrive advances the count)
     if (running_mean) {
       float f = momentum;
-      if (f < 0.f) f = 1.f / (float)(nbt[0] + 1);  // momentum=None: cumulative average
+      if (f < 0.f) f = 1.f / (float)((cma ? cma_arrive(nbt, C) : 0) + 1);  // momentum=None: cumulative average
       const double unb = M > 1 ? m2 / (double)(M - 1) : var;
       running_mean[c] = (1.f - f) * running_mean[c] + f * (float)mean;
       running_var[c] = (1.f - f) * running_var[c] + f * (float)unb;
     }
-    if (c == 0 && nbt) nbt[0] += 1;
+    if (c == 0 && nbt && !cma) nbt[0] += 1;
   }
 }
 
@@ -275,14 +291,15 @@ __global__ __launch_bounds__(256) void bn_fin_act_kernel(const float* __restrict
       stats[C + c] = invstd;
       stats[2 * C + c] = scale;
       stats[3 * C + c] = shift;
+      const bool cma = momentum < 0.f && running_mean && nbt;  // (cma_arrive advances the count)
       if (running_mean) {
         float f = momentum;
-        if (f < 0.f) f = 1.f / (float)(nbt[0] + 1);  // momentum=None: cumulative average
+        if (f < 0.f) f = 1.f / (float)((cma ? cma_arrive(nbt, C) : 0) + 1);  // momentum=None: cumulative average
         const double unb = M > 1 ? m2 / (double)(M - 1) : var;
         running_mean[c] = (1.f - f) * running_mean[c] + f * (float)mean;
         running_var[c] = (1.f - f) * running_var[c] + f * (float)unb;
       }
-      if (c == 0 && nbt) nbt[0] += 1;
+      if (c == 0 && nbt && !cma) nbt[0] += 1;
     }
   }
   __syncthreads();
