@@ -8,6 +8,13 @@
 // window and one per channel (block b into channel copy b % kActCopies). The slots are
 // zero-initialised by the host (a memset of the step's slot chunk, ops.cpp), so the value a
 // consumer reads is exactly the maximum over everything the producer wrote.
+//
+// Non-finite values: the folds below are plain fmaxf, which returns its non-NaN operand, so a NaN in
+// the activation is ignored and the slot holds the maximum of the other values (an inf is a value
+// and is kept). That is what the consumer needs: the maximum only chooses a power-of-two scale, the
+// NaN itself still sits in the activation and reaches every output that reads it through the GEMM,
+// and a NaN scale would spread it to the whole image or channel. The activation kernels' own ReLU
+// and max-pool do propagate NaN (relu_nan / max_nan, common.h).
 #pragma once
 #include "common.h"
 #include "kernels.h"

@@ -139,10 +139,10 @@ __device__ __forceinline__ float4 affine_act(float4 y, float4 sc, float4 sh, boo
   z.z = fmaf(y.z, sc.z, sh.z);
   z.w = fmaf(y.w, sc.w, sh.w);
   if (relu) {
-    z.x = fmaxf(z.x, 0.f);
-    z.y = fmaxf(z.y, 0.f);
-    z.z = fmaxf(z.z, 0.f);
-    z.w = fmaxf(z.w, 0.f);
+    z.x = relu_nan(z.x);
+    z.y = relu_nan(z.y);
+    z.z = relu_nan(z.z);
+    z.w = relu_nan(z.w);
   }
   return z;
 }
@@ -313,10 +313,10 @@ __global__ __launch_bounds__(256) void bn_fin_act_kernel(const float* __restrict
     if (pool) {
       const float4 z1 = affine_act(v[1], sc, sh, relu), z2 = affine_act(v[2], sc, sh, relu),
                    z3 = affine_act(v[3], sc, sh, relu);
-      z.x = fmaxf(fmaxf(z.x, z1.x), fmaxf(z2.x, z3.x));
-      z.y = fmaxf(fmaxf(z.y, z1.y), fmaxf(z2.y, z3.y));
-      z.z = fmaxf(fmaxf(z.z, z1.z), fmaxf(z2.z, z3.z));
-      z.w = fmaxf(fmaxf(z.w, z1.w), fmaxf(z2.w, z3.w));
+      z.x = max4_nan(z.x, z1.x, z2.x, z3.x);
+      z.y = max4_nan(z.y, z1.y, z2.y, z3.y);
+      z.z = max4_nan(z.z, z1.z, z2.z, z3.z);
+      z.w = max4_nan(z.w, z1.w, z2.w, z3.w);
     }
     st4(out + r * C + n0, z);
     if (want) {
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict
           z.x += r.x; z.y += r.y; z.z += r.z; z.w += r.w;
         }
         if (relu) {
-          z.x = fmaxf(z.x, 0.f); z.y = fmaxf(z.y, 0.f); z.z = fmaxf(z.z, 0.f); z.w = fmaxf(z.w, 0.f);
+          z.x = relu_nan(z.x); z.y = relu_nan(z.y); z.z = relu_nan(z.z); z.w = relu_nan(z.w);
         }
         finish(ib + 256 * u, pv[u], c4, z, k + u);
       }
@@ -439,10 +439,10 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict
       const float4 z2 = affine_act(ld4(base + (long long)W * C), sc, sh, relu);
       const float4 z3 = affine_act(ld4(base + (long long)W * C + C), sc, sh, relu);
       float4 z;
-      z.x = fmaxf(fmaxf(z0.x, z1.x), fmaxf(z2.x, z3.x));
-      z.y = fmaxf(fmaxf(z0.y, z1.y), fmaxf(z2.y, z3.y));
-      z.z = fmaxf(fmaxf(z0.z, z1.z), fmaxf(z2.z, z3.z));
-      z.w = fmaxf(fmaxf(z0.w, z1.w), fmaxf(z2.w, z3.w));
+      z.x = max4_nan(z0.x, z1.x, z2.x, z3.x);
+      z.y = max4_nan(z0.y, z1.y, z2.y, z3.y);
+      z.z = max4_nan(z0.z, z1.z, z2.z, z3.z);
+      z.w = max4_nan(z0.w, z1.w, z2.w, z3.w);
       finish(i, pix, c4, z, k);
     }
   }

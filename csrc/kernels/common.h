@@ -34,6 +34,17 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// NaN-propagating ReLU and max for forward activations (torch.relu, ATen's max-pool): fmaxf returns
+// its non-NaN operand, so relu(NaN) would be 0 and a pooling window would drop its NaNs. On
+// operands without a NaN both are fmaxf itself, bit for bit (relu(-0.0) included).
+__device__ __forceinline__ float relu_nan(float z) { return z != z ? z : fmaxf(z, 0.f); }
+__device__ __forceinline__ float max_nan(float a, float b) {
+  return __builtin_isunordered(a, b) ? a + b : fmaxf(a, b);  // (NaN + anything is NaN)
+}
+__device__ __forceinline__ float max4_nan(float a, float b, float c, float d) {
+  return max_nan(max_nan(a, b), max_nan(c, d));
+}
+
 // LDS barrier that does not wait for global loads still in flight: __syncthreads' fence would
 // drain them (vmcnt(0)). The release / acquire fences are workgroup-scope and LDS-only
 // ("local" address space), so they order the LDS stores before the barrier and the LDS loads after

@@ -1696,7 +1696,8 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restric
 
 // MaxPool2d(k, s, p) forward on NHWC with int32 argmax (flat h*W+w), and backward (scatter-add).
 // Max-pool on NHWC, float4 along C. The argmax is kept as the window-local tap index (uint8,
-// first max wins in (dh, dw) scan order like ATen), a quarter of an int32 index map.
+// first max wins in (dh, dw) scan order like ATen), a quarter of an int32 index map. A window that
+// holds a NaN returns NaN and the tap of its last NaN (ATen's val > max || isnan(val)).
 // 32-bit indices with multiply-shift division (the launchers check the sizes): the 64-bit divisions
 // the index decode took before were ~40 instructions each, four per element, in passes that are
 // otherwise bandwidth-bound
@@ -1727,7 +1728,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
         const int tap = dh * k + dw;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          if (vv[e] > m[e] || am[e] < 0) {
+          if (vv[e] > m[e] || am[e] < 0 || vv[e] != vv[e]) {  // a NaN always wins: the window's last one stays
             m[e] = vv[e];
             am[e] = tap;
           }

@@ -3024,6 +3024,9 @@ std::vector<at::Tensor> maxpool2d_fwd(const at::Tensor& x_, int64_t k, int64_t s
   const at::Tensor x = nhwc(x_);
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C % 4 == 0 && k * k <= 255, "maxpool2d: needs C % 4 == 0 and k*k <= 255");
+  // (beyond that a window can lie entirely in the padding and has no tap to return)
+  TORCH_CHECK(p >= 0 && p <= k / 2, "maxpool2d: pad should be at most half of the kernel size, but got pad=", p,
+              " and kernel size=", k);
   const int Ho = (H + 2 * p - k) / s + 1, Wo = (W + 2 * p - k) / s + 1;
   at::Tensor y = at::empty({N, C, Ho, Wo}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   at::Tensor arg = at::empty({N, C, Ho, Wo}, x.options().dtype(at::kByte).memory_format(at::MemoryFormat::ChannelsLast));

@@ -1,4 +1,4 @@
-"""Helpers of the BatchNorm stage tests (test_bn_stages_gpu.py): test data, the exact pass-through
+"""Helpers of the BatchNorm stage tests (test_bn_stages_gpu.py, test_nonfinite_gpu.py): test data, the exact pass-through
 conv that hands the BatchNorm kernels a chosen input and returns their dy, mirrors of the host's
 path selection (bn_bwd_grid, bn_fin_act_ok, bn_bwd_fin_apply_ok, chan_finalize_launch in
 csrc/kernels/bn.hip and conv_bn_act_fwd / conv_bn_act_bwd in csrc/runtime/ops.cpp), float64
@@ -133,6 +133,31 @@ def run_fwd(L, c, g, *, bias, pool, relu, training=True, affine=True, state=None
     xc = (c.x if x is None else x.cpu())
     want = xc + c.bias.view(1, -1, 1, 1) if bias else xc
     assert torch.equal(y.cpu(), want), "pass-through conv: y != fl(x + b)"
+    return r
+
+
+def run_fwd_nonfinite(L, c, g, *, x, b, want_y, pool, relu, training=True, state=None, res=None, drop_scale=None):
+    """run_fwd for inputs that hold NaN or inf (test_nonfinite_gpu.py): x, the conv bias b (or None),
+    the residual res (or None) and the stochastic-depth scales are device tensors given by the caller,
+    want_y (CPU) is what the pass-through conv must return for them. Through w = I an element x[n, k,
+    h, w] that is not finite makes every channel of its pixel non-finite (0 * NaN and 0 * inf are
+    NaN), so the precondition is not y == fl(x + b) but: NaN exactly where want_y has it, the same
+    inf where want_y has one, and bit-equal values everywhere else."""
+    from _nonfinite_util import agree_strict
+
+    M, C = c.M, c.C
+    force(L, "conv", 64, 64, 1, (M, C, C), (64, 64, 1))
+    w = eye_w(C)
+    rm, rv, nbt = state if state is not None else (None, None, None)
+    kw = {} if drop_scale is None else {"drop_scale": drop_scale}
+    out, y, stats, xs, _, xa, wa, rmask = L.conv_bn_act_fwd(x, w, b, g.gamma, g.beta, rm, rv, nbt, 0.1, EPS, training,
+                                                            1, 0, pool, relu, res, **kw)
+    r = types.SimpleNamespace(out=out, y=y, stats=stats, xs=xs, xa=xa, wa=wa, rmask=rmask, w=w, nparts=(M + 63) // 64)
+    y2, part, rpp = L.conv2d_fwd(x, w, b, 1, 0, True)
+    agree_strict(y, want_y, 0.0, name="pass-through conv, y against fl(x + b)")
+    agree_strict(y2, want_y, 0.0, name="pass-through conv2d_fwd, y against fl(x + b)")
+    assert int(rpp.item()) == 64 and tuple(part.shape) == (r.nparts, C, 2)
+    r.mean, r.var = merge_bn_partials(part, 64, M)  # non-finite in the channels whose y is
     return r
 
 
