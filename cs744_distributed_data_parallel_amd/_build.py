@@ -24,7 +24,7 @@ OUTPUT = os.path.join(PKG_DIR, "_C" + EXT_SUFFIX)
 
 KERNELS = ["conv_igemm.hip", "conv_x3.hip", "wgrad.hip", "bn.hip", "misc.hip", "stem.hip", "bwd_fuse.hip", "bwd_pair.hip",
            "bwd_pair_d128x128.hip", "bwd_pair_d128x64.hip", "bwd_pair_d64x128.hip", "bwd_pair_d64x64.hip",
-           "grad_norm.hip", "lars.hip", "adam.hip", "drop_path.hip", "randaug.hip"]
+           "grad_norm.hip", "lars.hip", "adam.hip", "drop_path.hip", "randaug.hip", "se.hip"]
 RUNTIME = ["ops.cpp", "rccl_comm.cpp", "reducer.cpp", "torch_ops.cpp", "bindings.cpp"]
 
 
@@ -50,6 +50,9 @@ def _hipcc() -> str:
 # adjacent scalar multiplies / FMAs into v_pk_mul_f32 / v_pk_fma_f32
 NO_SLP = {"conv_x3.hip", "wgrad.hip", "bwd_pair.hip", "bwd_pair_d128x128.hip", "bwd_pair_d128x64.hip",
           "bwd_pair_d64x128.hip", "bwd_pair_d64x64.hip"}
+# Memory-bound float4 kernels built without the packed-f32 VALU ops (v_pk_add / mul / fma_f32): the packed
+# forms buy a bandwidth-bound pass nothing, and scalar f32 keeps its arithmetic one plain FMA per element
+NO_PK_F32 = {"se.hip"}
 
 
 def _ninja_escape(s: str) -> str:
@@ -109,6 +112,8 @@ def write_ninja() -> str:
         lines.append(f"build {_ninja_escape(obj)}: kcc {_ninja_escape(src)}")
         if f in NO_SLP:
             lines.append("  kextra = -fno-slp-vectorize")
+        elif f in NO_PK_F32:
+            lines.append("  kextra = -Xclang -target-feature -Xclang -packed-fp32-ops")
         objs.append(obj)
     for f in RUNTIME:
         src = os.path.join(CSRC, "runtime", f)

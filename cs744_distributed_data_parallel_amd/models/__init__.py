@@ -1,5 +1,6 @@
 """Model zoo: the reference's VGG family (CIFAR-shaped) and the ResNet family (ImageNet-shaped)."""
-from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101, resnet152
+from .resnet import (ResNet, SEModule, resnet18, resnet34, resnet50, resnet101, resnet152, seresnet18, seresnet34,
+                     seresnet50, seresnet101, seresnet152)
 from .vgg import VGG, VGG11, VGG13, VGG16, VGG19, cfg, make_layers
 
 _REGISTRY = {
@@ -12,7 +13,14 @@ _REGISTRY = {
     "resnet50": resnet50,
     "resnet101": resnet101,
     "resnet152": resnet152,
+    "seresnet18": seresnet18,
+    "seresnet34": seresnet34,
+    "seresnet50": seresnet50,
+    "seresnet101": seresnet101,
+    "seresnet152": seresnet152,
 }
+# the Squeeze-and-Excitation models under their "resnetNN_se" spelling too (get_model strips "_" and "-")
+_REGISTRY.update({"resnet" + k[len("seresnet"):] + "se": v for k, v in list(_REGISTRY.items()) if k.startswith("seresnet")})
 
 # input shape (C, H, W) and number of classes per family
 INPUT_SHAPES = {k: ((3, 32, 32), 10) if k.startswith("vgg") else ((3, 224, 224), 1000) for k in _REGISTRY}
@@ -32,5 +40,6 @@ def list_models():
 __all__ = [
     "VGG", "VGG11", "VGG13", "VGG16", "VGG19", "cfg", "make_layers",
     "ResNet", "resnet18", "resnet34", "resnet50", "resnet101", "resnet152",
+    "SEModule", "seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152",
     "get_model", "list_models", "INPUT_SHAPES",
 ]

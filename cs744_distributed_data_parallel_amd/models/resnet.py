@@ -17,6 +17,10 @@ torchvision ``StochasticDepth(mode="row")``). The scale is applied inside the bl
 ``conv -> BN -> +residual -> ReLU`` (``conv_bn_act(..., drop_scale=)``); the draws of a step are one device
 launch keyed by a device step counter (csrc/kernels/drop_path.h), so a captured step drops different images
 at every replay.
+
+Squeeze-and-Excitation (``se=True``, the ``seresnetNN`` factories; timm's ``seresnetNN``): every block gates its
+branch per image and channel, ``relu(s * sigmoid(fc2(relu(fc1(mean_hw(u))))) * u + shortcut)`` with ``u`` the
+last BatchNorm's output, through ``CF.se_scale_act`` (csrc/kernels/se.hip).
 """
 from __future__ import annotations
 
@@ -34,22 +38,54 @@ from ..utils.arena import install_load_hooks
 _DEFER_DS = os.environ.get("CDP_DEFER_DS", "1") != "0"
 
 
+class SEModule(nn.Module):
+    """timm's ``SEModule``: ``x * sigmoid(fc2(relu(fc1(mean_hw(x)))))`` with two biased 1x1 convs and
+    ``Cr = max(1, round(channels * rd_ratio))`` hidden units (no channel rounding). Inside a block the fused
+    path reads ``fc1`` / ``fc2`` directly (``CF.se_scale_act``); this ``forward`` is the plain PyTorch gate."""
+
+    def __init__(self, channels, rd_ratio=1.0 / 16):
+        super().__init__()
+        rd = max(1, int(round(channels * rd_ratio)))
+        self.fc1 = nn.Conv2d(channels, rd, 1, bias=True)
+        self.fc2 = nn.Conv2d(rd, channels, 1, bias=True)
+
+    def forward(self, x):
+        g = torch.relu(self.fc1(x.mean((2, 3), keepdim=True)))
+        return x * torch.sigmoid(self.fc2(g))
+
+
+def _se_tail(block, x, out, conv, bn, ds):
+    """The native tail of an SE block: the last conv's plain BatchNorm output, the materialised shortcut, then
+    the gate, the stochastic-depth row, the residual add and the ReLU in ``CF.se_scale_act``. The shortcut's
+    two gradients (first conv / downsample, and the residual add) meet in an autograd add."""
+    u = CF.conv_bn_act(out, conv, bn, relu=False)
+    idt = x if block.downsample is None else CF.conv_bn_act(x, block.downsample[0], block.downsample[1], relu=False)
+    se = block.se
+    return CF.se_scale_act(u, idt, se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias, drop_scale=ds)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
     _drop_scale = None
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
         self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
         self.bn2 = nn.BatchNorm2d(planes)
+        if se:
+            self.se = SEModule(planes)
         self.downsample = downsample
         self.stride = stride
 
     def forward(self, x):
         ds = self._drop_scale  # this forward's stochastic-depth row (ResNet.forward), or None
+        se = getattr(self, "se", None)
+        if CF.use_native(x) and se is not None:
+            out = CF.conv_bn_act(x, self.conv1, self.bn1, relu=True)
+            return _se_tail(self, x, out, self.conv2, self.bn2, ds)
         if CF.use_native(x):
             sink = CF.GradSink.make(x)
             out = CF.conv_bn_act(x, self.conv1, self.bn1, relu=True, dx_sink=sink)
@@ -63,6 +99,8 @@ class BasicBlock(nn.Module):
         idt = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
+        if se is not None:
+            out = se(out)
         if ds is not None:
             out = out * ds.to(out.dtype).view(-1, 1, 1, 1)
         return self.relu(out + idt)
@@ -72,7 +110,7 @@ class Bottleneck(nn.Module):
     expansion = 4
     _drop_scale = None
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False):
         super().__init__()
         width = planes
         self.conv1 = nn.Conv2d(inplanes, width, 1, 1, 0, bias=False)
@@ -81,12 +119,19 @@ class Bottleneck(nn.Module):
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, planes * 4, 1, 1, 0, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
+        if se:
+            self.se = SEModule(planes * 4)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
 
     def forward(self, x):
         ds = self._drop_scale  # this forward's stochastic-depth row (ResNet.forward), or None
+        se = getattr(self, "se", None)
+        if CF.use_native(x) and se is not None:
+            out = CF.conv_bn_act(x, self.conv1, self.bn1, relu=True)
+            out = CF.conv_bn_act(out, self.conv2, self.bn2, relu=True)
+            return _se_tail(self, x, out, self.conv3, self.bn3, ds)
         if CF.use_native(x):
             # x's two gradients (conv1 + residual, or conv1 + downsample) are summed inside a
             # data-gradient GEMM epilogue instead of an autograd add (GradSink)
@@ -104,6 +149,8 @@ class Bottleneck(nn.Module):
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
+        if se is not None:
+            out = se(out)
         if ds is not None:
             out = out * ds.to(out.dtype).view(-1, 1, 1, 1)
         return self.relu(out + idt)
@@ -116,15 +163,17 @@ class ResNet(nn.Module):
     The rates, the counter and the table are plain attributes (the ``state_dict()`` keys stay torchvision's)
     that follow the module through ``.cuda()`` / ``.to()``. At 0.0 nothing is allocated or launched and
     ``drop_path_step`` is None. ``zero_init_residual``: every block's last BatchNorm weight starts at 0
-    (torchvision's rule), so every block starts as its shortcut."""
+    (torchvision's rule), so every block starts as its shortcut. ``se``: every block carries an
+    :class:`SEModule` (``layerL.B.se.fc1`` / ``fc2``) and gates its branch with it."""
 
     def __init__(self, block, layers, num_classes=1000, channels_last=True, drop_path_rate=0.0, drop_path_seed=0,
-                 zero_init_residual=False):
+                 zero_init_residual=False, se=False):
         super().__init__()
         if not 0.0 <= float(drop_path_rate) < 1.0:
             raise ValueError(f"drop_path_rate must be in [0, 1). Got: {drop_path_rate}")
         install_load_hooks(self)  # loaded weights refresh the optimizer's prepared products
         self.inplanes = 64
+        self._se = bool(se)
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -211,10 +260,11 @@ class ResNet(nn.Module):
                 nn.Conv2d(self.inplanes, planes * block.expansion, 1, stride, 0, bias=False),
                 nn.BatchNorm2d(planes * block.expansion),
             )
-        layers = [block(self.inplanes, planes, stride, downsample)]
+        kw = {"se": True} if self._se else {}
+        layers = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, **kw))
         return nn.Sequential(*layers)
 
     def forward(self, x):
@@ -238,7 +288,8 @@ class ResNet(nn.Module):
             # (stride-1 convs; the stem's input needs no gradient, stride-2 convs use sub-filters);
             # each conv module holds its entries for the duration of this forward (conv_bn_act
             # reads them)
-            convs = [m for m in self.modules() if isinstance(m, nn.Conv2d)]
+            # (an SE block's fc1 / fc2 feed no GEMM: se_scale_act reads them as they are)
+            convs = [m for n, m in self.named_modules() if isinstance(m, nn.Conv2d) and ".se." not in n]
             need = [m.stride[0] == 1 and (m is not self.conv1 or x.requires_grad) for m in convs]
             wam, wts = CF.weight_prep([m.weight for m in convs], need)
             for i, m in enumerate(convs):
@@ -278,3 +329,23 @@ def resnet101(**kw):
 
 def resnet152(**kw):
     return ResNet(Bottleneck, [3, 8, 36, 3], **kw)
+
+
+def seresnet18(**kw):
+    return ResNet(BasicBlock, [2, 2, 2, 2], se=True, **kw)
+
+
+def seresnet34(**kw):
+    return ResNet(BasicBlock, [3, 4, 6, 3], se=True, **kw)
+
+
+def seresnet50(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], se=True, **kw)
+
+
+def seresnet101(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], se=True, **kw)
+
+
+def seresnet152(**kw):
+    return ResNet(Bottleneck, [3, 8, 36, 3], se=True, **kw)

@@ -21,6 +21,7 @@ from .. import _native
 __all__ = [
     "GradSink",
     "conv_bn_act",
+    "se_scale_act",
     "drop_path_scales",
     "linear",
     "cross_entropy",
@@ -340,6 +341,59 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
     if pool:
         y = F.max_pool2d(y, 2, 2)
     return y
+
+
+# --------------------------------------------------------------------------- squeeze-and-excitation
+class _SEScaleAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, residual, w1, b1, w2, b2, drop_scale):
+        out, z, h, g, out_amax = _native.lib().se_scale_act_fwd(u, residual, w1, b1, w2, b2, drop_scale)
+        ctx.params = (w1, b1, w2, b2)
+        # the ReLU routing is read from `out` itself (out > 0)
+        ctx.save_for_backward(u, out, z, h, g, w1, w2, drop_scale)
+        _set_amax(out, out_amax)  # f16x2: the next block's GEMMs scale their operands from these slots
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        u, out, z, h, g, w1, w2, drop_scale = ctx.saved_tensors
+        w1p, b1p, w2p, b2p = ctx.params
+        nig = ctx.needs_input_grad
+        du, dr, dw1, db1, dw2, db2 = _native.lib().se_scale_act_bwd(
+            gout, u, out, z, h, g, w1, w2, drop_scale, nig[1],
+            _slot(w1p, nig[2]), _slot(b1p, nig[3]), _slot(w2p, nig[4]), _slot(b2p, nig[5]),
+        )
+        return (
+            du if nig[0] else None,
+            dr if nig[1] else None,
+            dw1 if nig[2] else None,
+            db1 if nig[3] else None,
+            dw2 if nig[4] else None,
+            db2 if nig[5] else None,
+            None,
+        )
+
+
+def se_scale_act(u, residual, w1, b1, w2, b2, drop_scale=None):
+    """The Squeeze-and-Excitation tail of a residual block: ``relu(s * g * u + residual)`` with the gate
+    ``g = sigmoid(W2 relu(W1 mean_hw(u) + b1) + b2)`` per image and channel.
+
+    ``u`` is the block's last BatchNorm output (``conv_bn_act(..., relu=False)``), ``residual`` its shortcut;
+    ``w1`` ``[Cr, C]`` / ``w2`` ``[C, Cr]`` may be the 1x1 convs' 4-D ``[., ., 1, 1]`` weights. ``drop_scale``
+    (stochastic depth): fp32 ``[N]``, multiplies image ``b``'s gated branch before the residual add; it gets
+    no gradient. GPU tensors with ``C % 4 == 0`` run the HIP kernels (csrc/kernels/se.hip: squeeze, excite and
+    one NHWC pass forward; reduce, excite, parameter gradients and one NHWC pass backward), anything else
+    this PyTorch composition.
+    """
+    if use_native(u) and u.shape[1] % 4 == 0:
+        return _SEScaleAct.apply(u, residual, w1, b1, w2, b2, drop_scale)
+    N, C = u.shape[0], u.shape[1]
+    z = u.mean((2, 3))
+    h = F.relu(F.linear(z, w1.reshape(-1, C), b1))
+    y = u * torch.sigmoid(F.linear(h, w2.reshape(C, -1), b2)).view(N, C, 1, 1)
+    if drop_scale is not None:
+        y = y * drop_scale.to(y.dtype).view(-1, 1, 1, 1)
+    return F.relu(y + residual)
 
 
 # --------------------------------------------------------------------------- stochastic depth

@@ -189,10 +189,15 @@ def test_model(model, test_loader, criterion, print_fn=print, topk=None):
     return float(test_loss), correct
 
 
+def _is_resnet(name: str) -> bool:
+    """The ImageNet-shaped ResNet family, its Squeeze-and-Excitation models (``seresnetNN``) included."""
+    return name.lower().replace("-", "").replace("_", "").startswith(("resnet", "seresnet"))
+
+
 def build_data(args, device, train: bool):
     if args.data.startswith("cifar10-bin:"):
         return cifar10_binary(args.data.split(":", 1)[1], train=train, device=device)
-    if args.model.startswith("resnet"):
+    if _is_resnet(args.model):
         n = args.synthetic_size or (1281 if train else 500)
         return synthetic_imagenet(n, seed=0 if train else 1, device=device, size=args.stored_size)
     n = args.synthetic_size or (50000 if train else 10000)
@@ -237,7 +242,7 @@ def run(rank, size, epochs, batch_size, args):
         criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
     eval_criterion = CrossEntropyLoss()
     model_kw = {}
-    if args.model.startswith("resnet"):
+    if _is_resnet(args.model):
         # stochastic depth and the zero-initialised last BatchNorm live in the model; every rank draws its own
         # masks (its seed is derived from --seed and the rank)
         model_kw = dict(drop_path_rate=args.drop_path, drop_path_seed=args.seed * 1000003 + rank,
@@ -496,7 +501,7 @@ def parse_args(argv=None):
         p.error("--bce-target-thresh and --bce-sum-classes need --loss bce")
     if args.bce_target_thresh is not None and not 0.0 <= args.bce_target_thresh < 1.0:
         p.error("--bce-target-thresh must be in [0, 1)")
-    if not args.model.lower().startswith("resnet") and (args.drop_path != 0.0 or args.zero_init_residual):
+    if not _is_resnet(args.model) and (args.drop_path != 0.0 or args.zero_init_residual):
         p.error("--drop-path and --zero-init-residual apply to the resnet models only")
     if not 0.0 <= args.drop_path < 1.0:
         p.error("--drop-path must be in [0, 1)")

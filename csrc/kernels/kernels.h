@@ -308,6 +308,40 @@ void drop_path_draw_launch(long long* counter, unsigned long long seed, const fl
 void drop_path_table_launch(unsigned long long seed, long long first, long long n, const float* rates, int nb, int B,
                             float* out, hipStream_t st);
 
+// se.hip: the Squeeze-and-Excitation tail of a residual block, out = relu(s[n] g[n][c] u + r) with
+// g = sigmoid(W2 relu(W1 mean_hw(u) + b1) + b2); u, r, out NHWC [N][HW][C], C % 4 == 0, C <= kMaxSeC,
+// W1 [Cr][C], W2 [C][Cr], 1 <= Cr <= kMaxSeCr. Every NHWC kernel runs one workgroup per (image, pixel
+// chunk) of an SeSplit; the reductions leave one partial row per workgroup, part[N][nchunk][C], which
+// the per-image kernels sum in ascending chunk order.
+constexpr int kMaxSeC = 2048;  // = kMaxActC (act_max.h): the act-max channel table of the scale pass
+constexpr int kMaxSeCr = 256;
+struct SeSplit {
+  int nchunk, cpix;  // chunks per image, pixels per chunk (the last one may be shorter)
+};
+// reduce: the split of the two reductions (one chunk for a small map such as 7 x 7), else of the passes;
+// cus: the device's compute units (enough workgroups to fill them at the large maps)
+SeSplit se_split(int N, int HW, int C, bool reduce, int cus);
+void se_squeeze_launch(const float* u, int N, int HW, int C, SeSplit sp, float* part, hipStream_t st);
+// z [N][C] (the mean), h [N][Cr], g [N][C] from the squeeze's partials
+void se_excite_launch(const float* part, int nchunk, const float* w1, const float* b1, const float* w2,
+                      const float* b2, int N, int HW, int C, int Cr, float* z, float* h, float* g, hipStream_t st);
+// drop_scale (or nullptr): fp32 [N], the stochastic-depth row s; am: out's act max (ActMaxOut)
+void se_scale_act_launch(const float* u, const float* r, const float* g, const float* drop_scale, float* out, int N,
+                         int HW, int C, SeSplit sp, ActMaxOut am, hipStream_t st);
+// part[n][chunk][c] = sum over the chunk of gout * (out > 0) * u
+void se_bwd_reduce_launch(const float* gout, const float* out, const float* u, int N, int HW, int C, SeSplit sp,
+                          float* part, hipStream_t st);
+// da2 [N][C], da1 [N][Cr] (the two layers' pre-activation gradients), dpool [N][C] (the squeeze's, per pixel)
+void se_excite_bwd_launch(const float* part, int nchunk, const float* w1, const float* w2, const float* h,
+                          const float* g, const float* drop_scale, int N, int HW, int C, int Cr, float* da2,
+                          float* da1, float* dpool, hipStream_t st);
+void se_param_grad_launch(const float* da1, const float* da2, const float* z, const float* h, int N, int C, int Cr,
+                          float* dw1, float* db1, float* dw2, float* db2, hipStream_t st);
+// du = dz (s g) + dpool, dr = dz (nullptr: not wanted), dz = gout * (out > 0)
+void se_bwd_apply_launch(const float* gout, const float* out, const float* g, const float* dpool,
+                         const float* drop_scale, float* du, float* dr, int N, int HW, int C, SeSplit sp,
+                         hipStream_t st);
+
 // misc.hip
 // eps: label smoothing in [0, 1] (target distribution (1 - eps) onehot + eps / C; 0: the plain kernels'
 // arithmetic); topk >= 1: a row counts as correct when fewer than topk logits rank above its target's

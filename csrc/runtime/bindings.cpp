@@ -283,6 +283,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("maxpool2d_bwd", &maxpool2d_bwd);
   m.def("avgpool_fwd", &avgpool_fwd);
   m.def("avgpool_bwd", &avgpool_bwd);
+  m.def("se_scale_act_fwd", &se_scale_act_fwd, py::arg("u"), py::arg("residual"), py::arg("w1"), py::arg("b1"),
+        py::arg("w2"), py::arg("b2"), py::arg("drop_scale") = py::none(),
+        "Squeeze-and-Excitation block tail: (out, z, h, g, out's act max) with out = relu(s g u + residual)");
+  m.def("se_scale_act_bwd", &se_scale_act_bwd, py::arg("gout"), py::arg("u"), py::arg("out"), py::arg("z"),
+        py::arg("h"), py::arg("g"), py::arg("w1"), py::arg("w2"), py::arg("drop_scale"), py::arg("need_dr"),
+        py::arg("dw1_out") = py::none(), py::arg("db1_out") = py::none(), py::arg("dw2_out") = py::none(),
+        py::arg("db2_out") = py::none(), "(du, dr, dw1, db1, dw2, db2) of se_scale_act_fwd");
 
   // -------------------------------------------------------------- RCCL
   py::class_<RcclWork, std::shared_ptr<RcclWork>>(m, "RcclWork")

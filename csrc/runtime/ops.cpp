@@ -3063,6 +3063,127 @@ at::Tensor avgpool_bwd(const at::Tensor& gy_, std::vector<int64_t> in_shape) {
   return gx;
 }
 
+// ---------------------------------------------------------------- squeeze-and-excitation (se.hip)
+namespace {
+// an SE layer's weight as dense rows [O][I]: 2-D, or the 1x1 conv's 4-D [O, I, 1, 1] in either memory format
+at::Tensor se_weight(const at::Tensor& w, int64_t O, int64_t I, const char* name) {
+  check_f32_cuda(w, name);
+  TORCH_CHECK((w.dim() == 2 || (w.dim() == 4 && w.size(2) == 1 && w.size(3) == 1)) && w.size(0) == O && w.size(1) == I,
+              "se_scale_act: ", name, " must be [", O, ", ", I, "] or [", O, ", ", I, ", 1, 1], got ", w.sizes());
+  return w.reshape({O, I}).contiguous();
+}
+at::Tensor se_bias(const at::Tensor& b, int64_t O, const char* name) {
+  check_f32_cuda(b, name);
+  TORCH_CHECK(b.dim() == 1 && b.size(0) == O, "se_scale_act: ", name, " must be [", O, "], got ", b.sizes());
+  return b.contiguous();
+}
+// a parameter gradient's destination: the given arena slot (shaped like the parameter), else a new tensor
+at::Tensor se_grad_dst(const c10::optional<at::Tensor>& slot, const at::Tensor& like, const char* name) {
+  if (!slot.has_value() || !slot->defined()) return at::empty_like(like);
+  TORCH_CHECK(slot->is_cuda() && slot->scalar_type() == at::kFloat && slot->numel() == like.numel() &&
+                  slot->is_non_overlapping_and_dense(),
+              "se_scale_act_bwd: the ", name, " slot must be a dense float32 tensor of the parameter's size");
+  return *slot;
+}
+struct SeDims {
+  int N, C, H, W, HW, Cr;
+};
+SeDims se_dims(const at::Tensor& u, const at::Tensor& w1, const char* op) {
+  TORCH_CHECK(u.dim() == 4, op, ": u must be [N, C, H, W]");
+  const int64_t N = u.size(0), C = u.size(1), H = u.size(2), W = u.size(3), Cr = w1.size(0);
+  TORCH_CHECK(N > 0 && H * W > 0, op, ": empty input");
+  TORCH_CHECK(C % 4 == 0 && C <= kMaxSeC, op, ": needs C % 4 == 0 and C <= ", kMaxSeC, ", got C = ", C);
+  TORCH_CHECK(Cr >= 1 && Cr <= kMaxSeCr, op, ": needs 1 <= Cr <= ", kMaxSeCr, ", got Cr = ", Cr);
+  TORCH_CHECK(N * H * W * C < (1LL << 31), op, ": N * H * W * C = ", N * H * W * C,
+              " does not fit the kernels' 32-bit pixel indexing (must be < 2^31)");
+  return {(int)N, (int)C, (int)H, (int)W, (int)(H * W), (int)Cr};
+}
+}  // namespace
+
+// {out, z, h, g, out's act max (f16x2 engine, else undefined)}
+std::vector<at::Tensor> se_scale_act_fwd(const at::Tensor& u_, const at::Tensor& residual, const at::Tensor& w1_,
+                                         const at::Tensor& b1_, const at::Tensor& w2_, const at::Tensor& b2_,
+                                         const c10::optional<at::Tensor>& drop_scale) {
+  check_f32_cuda(u_, "u");
+  check_f32_cuda(residual, "residual");
+  const SeDims d = se_dims(u_, w1_, "se_scale_act_fwd");
+  TORCH_CHECK(residual.sizes() == u_.sizes(), "se_scale_act_fwd: the residual must have u's shape");
+  const at::Tensor u = nhwc(u_), r = nhwc(residual);
+  const at::Tensor w1 = se_weight(w1_, d.Cr, d.C, "w1"), w2 = se_weight(w2_, d.C, d.Cr, "w2");
+  TORCH_CHECK(aligned16(w1), "se_scale_act: w1 must be 16-byte aligned (its rows are read as float4)");
+  const at::Tensor b1 = se_bias(b1_, d.Cr, "b1"), b2 = se_bias(b2_, d.C, "b2");
+  const float* dsp = drop_scale_ptr(drop_scale, u, "se_scale_act_fwd");
+  hipStream_t st = cur_stream();
+  auto opts = u.options();
+  const SeSplit rs = se_split(d.N, d.HW, d.C, true, num_cus()), ps = se_split(d.N, d.HW, d.C, false, num_cus());
+  at::Tensor part = at::empty({d.N, rs.nchunk, d.C}, opts);
+  at::Tensor z = at::empty({d.N, d.C}, opts), h = at::empty({d.N, d.Cr}, opts), g = at::empty({d.N, d.C}, opts);
+  at::Tensor out = at::empty({d.N, d.C, d.H, d.W}, opts.memory_format(at::MemoryFormat::ChannelsLast));
+  se_squeeze_launch(u.data_ptr<float>(), d.N, d.HW, d.C, rs, part.data_ptr<float>(), st);
+  se_excite_launch(part.data_ptr<float>(), rs.nchunk, w1.data_ptr<float>(), b1.data_ptr<float>(),
+                   w2.data_ptr<float>(), b2.data_ptr<float>(), d.N, d.HW, d.C, d.Cr, z.data_ptr<float>(),
+                   h.data_ptr<float>(), g.data_ptr<float>(), st);
+  at::Tensor out_amax;  // the output's act max: the next block's operand scales (f16x2)
+  ActMaxOut am{nullptr, nullptr};
+  if (f16x2_mode()) {
+    out_amax = new_act_max(d.N, d.C, out, st);
+    am = act_out(out_amax, d.N);
+  }
+  se_scale_act_launch(u.data_ptr<float>(), r.data_ptr<float>(), g.data_ptr<float>(), dsp, out.data_ptr<float>(), d.N,
+                      d.HW, d.C, ps, am, st);
+  return {out, z, h, g, out_amax};
+}
+
+// {du, dr (undefined when !need_dr), dw1, db1, dw2, db2}; the parameter gradients are written into the given
+// slots (shaped like the parameters) or into new tensors shaped like w1 / w2
+std::vector<at::Tensor> se_scale_act_bwd(const at::Tensor& gout_, const at::Tensor& u_, const at::Tensor& out_,
+                                         const at::Tensor& z, const at::Tensor& h, const at::Tensor& g,
+                                         const at::Tensor& w1_, const at::Tensor& w2_,
+                                         const c10::optional<at::Tensor>& drop_scale, bool need_dr,
+                                         const c10::optional<at::Tensor>& dw1_out,
+                                         const c10::optional<at::Tensor>& db1_out,
+                                         const c10::optional<at::Tensor>& dw2_out,
+                                         const c10::optional<at::Tensor>& db2_out) {
+  check_f32_cuda(gout_, "grad_output");
+  check_f32_cuda(u_, "u");
+  check_f32_cuda(out_, "out");
+  const SeDims d = se_dims(u_, w1_, "se_scale_act_bwd");
+  TORCH_CHECK(gout_.sizes() == u_.sizes() && out_.sizes() == u_.sizes(),
+              "se_scale_act_bwd: grad_output and out must have u's shape");
+  const at::Tensor gout = nhwc(gout_), u = nhwc(u_), out = nhwc(out_);
+  const at::Tensor w1 = se_weight(w1_, d.Cr, d.C, "w1"), w2 = se_weight(w2_, d.C, d.Cr, "w2");
+  TORCH_CHECK(aligned16(w1), "se_scale_act: w1 must be 16-byte aligned (its rows are read as float4)");
+  // the gradients are written in the weights' own element order
+  TORCH_CHECK(w1.data_ptr() == w1_.data_ptr() && w2.data_ptr() == w2_.data_ptr(),
+              "se_scale_act_bwd: w1 / w2 must be stored as dense rows [Cr][C] / [C][Cr]");
+  for (const at::Tensor* t : {&z, &h, &g}) check_f32_cuda(*t, "saved z / h / g");
+  TORCH_CHECK(z.is_contiguous() && z.numel() == (int64_t)d.N * d.C && g.is_contiguous() &&
+                  g.numel() == (int64_t)d.N * d.C && h.is_contiguous() && h.numel() == (int64_t)d.N * d.Cr,
+              "se_scale_act_bwd: z, g must be contiguous [N, C] and h [N, Cr]");
+  const float* dsp = drop_scale_ptr(drop_scale, u, "se_scale_act_bwd");
+  hipStream_t st = cur_stream();
+  auto opts = u.options();
+  const SeSplit rs = se_split(d.N, d.HW, d.C, true, num_cus()), ps = se_split(d.N, d.HW, d.C, false, num_cus());
+  at::Tensor part = at::empty({d.N, rs.nchunk, d.C}, opts);
+  at::Tensor da2 = at::empty({d.N, d.C}, opts), da1 = at::empty({d.N, d.Cr}, opts), dpool = at::empty({d.N, d.C}, opts);
+  at::Tensor dw1 = se_grad_dst(dw1_out, w1_, "dW1"), dw2 = se_grad_dst(dw2_out, w2_, "dW2");
+  at::Tensor db1 = se_grad_dst(db1_out, h.select(0, 0), "db1"), db2 = se_grad_dst(db2_out, g.select(0, 0), "db2");
+  auto nhwc_opts = opts.memory_format(at::MemoryFormat::ChannelsLast);
+  at::Tensor du = at::empty({d.N, d.C, d.H, d.W}, nhwc_opts);
+  at::Tensor dr = need_dr ? at::empty({d.N, d.C, d.H, d.W}, nhwc_opts) : at::Tensor();
+  se_bwd_reduce_launch(gout.data_ptr<float>(), out.data_ptr<float>(), u.data_ptr<float>(), d.N, d.HW, d.C, rs,
+                       part.data_ptr<float>(), st);
+  se_excite_bwd_launch(part.data_ptr<float>(), rs.nchunk, w1.data_ptr<float>(), w2.data_ptr<float>(),
+                       h.data_ptr<float>(), g.data_ptr<float>(), dsp, d.N, d.HW, d.C, d.Cr, da2.data_ptr<float>(),
+                       da1.data_ptr<float>(), dpool.data_ptr<float>(), st);
+  se_param_grad_launch(da1.data_ptr<float>(), da2.data_ptr<float>(), z.data_ptr<float>(), h.data_ptr<float>(), d.N,
+                       d.C, d.Cr, dw1.data_ptr<float>(), db1.data_ptr<float>(), dw2.data_ptr<float>(),
+                       db2.data_ptr<float>(), st);
+  se_bwd_apply_launch(gout.data_ptr<float>(), out.data_ptr<float>(), g.data_ptr<float>(), dpool.data_ptr<float>(),
+                      dsp, du.data_ptr<float>(), need_dr ? dr.data_ptr<float>() : nullptr, d.N, d.HW, d.C, ps, st);
+  return {du, dr, dw1, db1, dw2, db2};
+}
+
 
 std::vector<std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>> gemm_log(bool clear) {
   return gemm_log_snapshot(clear);

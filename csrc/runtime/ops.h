@@ -258,6 +258,21 @@ at::Tensor maxpool2d_bwd(const at::Tensor& gy, const at::Tensor& arg, std::vecto
                          int64_t s, int64_t p);
 at::Tensor avgpool_fwd(const at::Tensor& x);
 at::Tensor avgpool_bwd(const at::Tensor& gy, std::vector<int64_t> in_shape);
+// Squeeze-and-Excitation tail of a residual block (se.hip): out = relu(s[n] g[n][c] u + residual),
+// g = sigmoid(W2 relu(W1 mean_hw(u) + b1) + b2); w1 [Cr, C] / w2 [C, Cr], 2-D or the 1x1 convs' 4-D weights.
+// {out, z, h, g, out's act max (f16x2 engine)}
+std::vector<at::Tensor> se_scale_act_fwd(const at::Tensor& u, const at::Tensor& residual, const at::Tensor& w1,
+                                         const at::Tensor& b1, const at::Tensor& w2, const at::Tensor& b2,
+                                         const c10::optional<at::Tensor>& drop_scale);
+// {du, dr (need_dr), dw1, db1, dw2, db2}; the *_out slots receive the parameter gradients in place
+std::vector<at::Tensor> se_scale_act_bwd(const at::Tensor& gout, const at::Tensor& u, const at::Tensor& out,
+                                         const at::Tensor& z, const at::Tensor& h, const at::Tensor& g,
+                                         const at::Tensor& w1, const at::Tensor& w2,
+                                         const c10::optional<at::Tensor>& drop_scale, bool need_dr,
+                                         const c10::optional<at::Tensor>& dw1_out,
+                                         const c10::optional<at::Tensor>& db1_out,
+                                         const c10::optional<at::Tensor>& dw2_out,
+                                         const c10::optional<at::Tensor>& db2_out);
 
 // CDP_GEMM_LOG=1: the GEMM launches so far as (kind, M, N, K, bm, bn, splits), in enqueue order
 std::vector<std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>> gemm_log(bool clear);
