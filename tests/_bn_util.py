@@ -362,11 +362,34 @@ def check_sums_and_dy(wst, ref, dy, dbeta, dgamma, K, sums=None):
     dyr = ref.sc * (ref.dz - k1 - ref.xh * k2)
     bound = ref.sc.abs() * (2.0 ** -21 * (ref.dz.abs() + k1.abs() + (ref.xh * k2).abs())
                             + _cv(B0) / ref.M + ref.xh.abs() * _cv(B1) / ref.M)
-    got = dy.double().cpu()
-    assert torch.isfinite(got).all()
-    got = torch.where(ref.amb, dyr, got)
-    wst.add("dy", got, dyr, bound)
+    if dy is not None:  # (None: the caller's kernel never writes dy -- the stem weight gradient)
+        got = dy.double().cpu()
+        assert torch.isfinite(got).all()
+        got = torch.where(ref.amb, dyr, got)
+        wst.add("dy", got, dyr, bound)
     return dyr, bound, B0, B1
+
+
+def check_db(wst, ref, db, dyr, dybound, B0, B1, K, training, has_bias, pool, nblk):
+    """The conv-bias gradient sum(dy). Training: -scale S2 S1 / M with S2 = sum xhat, exactly 0, within
+    |sc| fp32_bound(sum |xhat|, K) (|S1| + B1) / M; eval: scale S0; a pooled odd map: bn_bwd_apply's
+    partial sums of dy over nblk blocks, finalized by chan_finalize."""
+    if not has_bias:
+        assert db is None
+        return
+    sc = ref.sc.view(-1)
+    odd = pool and (ref.H % 2 == 1 or ref.W % 2 == 1)
+    if odd:
+        npix = ref.N * (ref.H // 2) * (ref.W // 2)
+        Kdb = 4 * -(-npix // nblk) + -(-ref.M // nblk)
+        # (an ambiguous element's dy may differ by |sc| |g|: slack0)
+        bound = dybound.sum((0, 2, 3)) + fp32_bound(dyr.abs().sum((0, 2, 3)), Kdb) + sc.abs() * ref.slack0
+        wst.add("db(sum dy)", db, dyr.sum((0, 2, 3)), bound)
+    elif training:
+        bound = sc.abs() * fp32_bound(ref.A2, K) * (ref.S1.abs() + B1) / ref.M
+        wst.add("db(0)", db, torch.zeros_like(ref.S0), bound)
+    else:
+        wst.add("db(eval)", db, sc * ref.S0, sc.abs() * B0 + U * (sc * ref.S0).abs())
 
 
 def split_rows(S, nparts, gen):

@@ -53,7 +53,7 @@ import torch
 import torch.nn.functional as F
 
 from _bn_util import (BWD_REDUCE_ROWS, EPS, U, Worst, act_qmode, assert_dgrad_passthrough, bn_bwd_grid, bn_case,
-                      bn_case_gpu, bwd_path, bwd_ref, check_out, check_stats_eval, check_stats_train,
+                      bn_case_gpu, bwd_path, bwd_ref, check_db, check_out, check_stats_eval, check_stats_train,
                       check_sums_and_dy, cl, force, fp32_bound, fwd_path, lib, momentum_factor, new_state,
                       running_ref, run_fwd, set_env, split_rows, sum_K, _cv)
 
@@ -244,23 +244,7 @@ def test_momentum_none_is_cumulative_average(L, monkeypatch, C, shp, fin_env, pa
 
 
 # ------------------------------------------------------------------------------ backward
-def _db_check(wst, ref, db, dyr, dybound, B0, B1, K, training, has_bias, pool, nblk):
-    if not has_bias:
-        assert db is None
-        return
-    sc = ref.sc.view(-1)
-    odd = pool and (ref.H % 2 == 1 or ref.W % 2 == 1)
-    if odd:  # bn_bwd_apply's partial sums of dy, finalized by chan_finalize
-        npix = ref.N * (ref.H // 2) * (ref.W // 2)
-        Kdb = 4 * -(-npix // nblk) + -(-ref.M // nblk)
-        # (an ambiguous element's dy may differ by |sc| |g|: slack0)
-        bound = dybound.sum((0, 2, 3)) + fp32_bound(dyr.abs().sum((0, 2, 3)), Kdb) + sc.abs() * ref.slack0
-        wst.add("db(sum dy)", db, dyr.sum((0, 2, 3)), bound)
-    elif training:  # -scale S2 S1 / M with S2 = sum xhat: exactly 0
-        bound = sc.abs() * fp32_bound(ref.A2, K) * (ref.S1.abs() + B1) / ref.M
-        wst.add("db(0)", db, torch.zeros_like(ref.S0), bound)
-    else:
-        wst.add("db(eval)", db, sc * ref.S0, sc.abs() * B0 + U * (sc * ref.S0).abs())
+_db_check = check_db  # (shared with the stem tests)
 
 
 def _bwd(L, monkeypatch, name, C, shp, bias, pool, relu, fin_env, path, training=True, nparts_range=None):
