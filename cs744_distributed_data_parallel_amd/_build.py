@@ -24,7 +24,7 @@ OUTPUT = os.path.join(PKG_DIR, "_C" + EXT_SUFFIX)
 
 KERNELS = ["conv_igemm.hip", "conv_x3.hip", "wgrad.hip", "bn.hip", "misc.hip", "stem.hip", "bwd_fuse.hip", "bwd_pair.hip",
            "bwd_pair_d128x128.hip", "bwd_pair_d128x64.hip", "bwd_pair_d64x128.hip", "bwd_pair_d64x64.hip",
-           "grad_norm.hip", "lars.hip", "adam.hip", "drop_path.hip", "randaug.hip", "se.hip"]
+           "grad_norm.hip", "lars.hip", "adam.hip", "drop_path.hip", "randaug.hip", "se.hip", "gn.hip"]
 RUNTIME = ["ops.cpp", "rccl_comm.cpp", "reducer.cpp", "torch_ops.cpp", "bindings.cpp"]
 
 
@@ -52,7 +52,7 @@ NO_SLP = {"conv_x3.hip", "wgrad.hip", "bwd_pair.hip", "bwd_pair_d128x128.hip", "
           "bwd_pair_d64x128.hip", "bwd_pair_d64x64.hip"}
 # Memory-bound float4 kernels built without the packed-f32 VALU ops (v_pk_add / mul / fma_f32): the packed
 # forms buy a bandwidth-bound pass nothing, and scalar f32 keeps its arithmetic one plain FMA per element
-NO_PK_F32 = {"se.hip"}
+NO_PK_F32 = {"se.hip", "gn.hip"}
 
 
 def _ninja_escape(s: str) -> str:

@@ -1,6 +1,7 @@
 """Model zoo: the reference's VGG family (CIFAR-shaped) and the ResNet family (ImageNet-shaped)."""
-from .resnet import (ResNet, SEModule, resnet18, resnet34, resnet50, resnet101, resnet152, seresnet18, seresnet34,
-                     seresnet50, seresnet101, seresnet152)
+from .resnet import (ResNet, SEModule, resnet18, resnet18_gn, resnet34, resnet34_gn, resnet50, resnet50_gn, resnet101,
+                     resnet101_gn, resnet152, resnet152_gn, seresnet18, seresnet34, seresnet50, seresnet101,
+                     seresnet152)
 from .vgg import VGG, VGG11, VGG13, VGG16, VGG19, cfg, make_layers
 
 _REGISTRY = {
@@ -18,6 +19,12 @@ _REGISTRY = {
     "seresnet50": seresnet50,
     "seresnet101": seresnet101,
     "seresnet152": seresnet152,
+    # GroupNorm in place of every BatchNorm ("resnet50_gn": get_model strips "_" and "-")
+    "resnet18gn": resnet18_gn,
+    "resnet34gn": resnet34_gn,
+    "resnet50gn": resnet50_gn,
+    "resnet101gn": resnet101_gn,
+    "resnet152gn": resnet152_gn,
 }
 # the Squeeze-and-Excitation models under their "resnetNN_se" spelling too (get_model strips "_" and "-")
 _REGISTRY.update({"resnet" + k[len("seresnet"):] + "se": v for k, v in list(_REGISTRY.items()) if k.startswith("seresnet")})
@@ -40,6 +47,7 @@ def list_models():
 __all__ = [
     "VGG", "VGG11", "VGG13", "VGG16", "VGG19", "cfg", "make_layers",
     "ResNet", "resnet18", "resnet34", "resnet50", "resnet101", "resnet152",
+    "resnet18_gn", "resnet34_gn", "resnet50_gn", "resnet101_gn", "resnet152_gn",
     "SEModule", "seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152",
     "get_model", "list_models", "INPUT_SHAPES",
 ]

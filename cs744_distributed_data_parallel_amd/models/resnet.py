@@ -21,9 +21,16 @@ at every replay.
 Squeeze-and-Excitation (``se=True``, the ``seresnetNN`` factories; timm's ``seresnetNN``): every block gates its
 branch per image and channel, ``relu(s * sigmoid(fc2(relu(fc1(mean_hw(u))))) * u + shortcut)`` with ``u`` the
 last BatchNorm's output, through ``CF.se_scale_act`` (csrc/kernels/se.hip).
+
+GroupNorm (``norm="gn"``, the ``resnetNN_gn`` factories; torchvision's ``norm_layer=GroupNorm``, timm's
+``resnet50_gn``): every norm is an ``nn.GroupNorm(gn_groups, C)`` under the BatchNorm's attribute name, so the
+``state_dict()`` is ``resnetNN``'s minus the running statistics. Its statistics are per image: no buffers, nothing
+that depends on how a batch is cut across ranks. Every ``conv -> GN [-> +shortcut] [-> ReLU]`` is
+``CF.conv_gn_act`` (csrc/kernels/gn.hip); the shortcut's two gradients meet in an autograd add.
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import torch
@@ -64,17 +71,24 @@ def _se_tail(block, x, out, conv, bn, ds):
     return CF.se_scale_act(u, idt, se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias, drop_scale=ds)
 
 
+def _gn_tail(block, x, out, conv, gn, ds):
+    """The native tail of a GroupNorm block: the materialised shortcut, then the last conv with its GroupNorm, the
+    stochastic-depth row, the residual add and the ReLU in ``CF.conv_gn_act``."""
+    idt = x if block.downsample is None else CF.conv_gn_act(x, block.downsample[0], block.downsample[1], relu=False)
+    return CF.conv_gn_act(out, conv, gn, relu=True, residual=idt, drop_scale=ds)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
     _drop_scale = None
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False, norm=nn.BatchNorm2d):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn1 = norm(planes)
         self.relu = nn.ReLU(inplace=True)
         self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
+        self.bn2 = norm(planes)
         if se:
             self.se = SEModule(planes)
         self.downsample = downsample
@@ -83,6 +97,9 @@ class BasicBlock(nn.Module):
     def forward(self, x):
         ds = self._drop_scale  # this forward's stochastic-depth row (ResNet.forward), or None
         se = getattr(self, "se", None)
+        if CF.use_native(x) and isinstance(self.bn1, nn.GroupNorm):
+            out = CF.conv_gn_act(x, self.conv1, self.bn1, relu=True)
+            return _gn_tail(self, x, out, self.conv2, self.bn2, ds)
         if CF.use_native(x) and se is not None:
             out = CF.conv_bn_act(x, self.conv1, self.bn1, relu=True)
             return _se_tail(self, x, out, self.conv2, self.bn2, ds)
@@ -110,15 +127,15 @@ class Bottleneck(nn.Module):
     expansion = 4
     _drop_scale = None
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False, norm=nn.BatchNorm2d):
         super().__init__()
         width = planes
         self.conv1 = nn.Conv2d(inplanes, width, 1, 1, 0, bias=False)
-        self.bn1 = nn.BatchNorm2d(width)
+        self.bn1 = norm(width)
         self.conv2 = nn.Conv2d(width, width, 3, stride, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(width)
+        self.bn2 = norm(width)
         self.conv3 = nn.Conv2d(width, planes * 4, 1, 1, 0, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.bn3 = norm(planes * 4)
         if se:
             self.se = SEModule(planes * 4)
         self.relu = nn.ReLU(inplace=True)
@@ -128,6 +145,10 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         ds = self._drop_scale  # this forward's stochastic-depth row (ResNet.forward), or None
         se = getattr(self, "se", None)
+        if CF.use_native(x) and isinstance(self.bn1, nn.GroupNorm):
+            out = CF.conv_gn_act(x, self.conv1, self.bn1, relu=True)
+            out = CF.conv_gn_act(out, self.conv2, self.bn2, relu=True)
+            return _gn_tail(self, x, out, self.conv3, self.bn3, ds)
         if CF.use_native(x) and se is not None:
             out = CF.conv_bn_act(x, self.conv1, self.bn1, relu=True)
             out = CF.conv_bn_act(out, self.conv2, self.bn2, relu=True)
@@ -164,18 +185,31 @@ class ResNet(nn.Module):
     that follow the module through ``.cuda()`` / ``.to()``. At 0.0 nothing is allocated or launched and
     ``drop_path_step`` is None. ``zero_init_residual``: every block's last BatchNorm weight starts at 0
     (torchvision's rule), so every block starts as its shortcut. ``se``: every block carries an
-    :class:`SEModule` (``layerL.B.se.fc1`` / ``fc2``) and gates its branch with it."""
+    :class:`SEModule` (``layerL.B.se.fc1`` / ``fc2``) and gates its branch with it. ``norm``: ``"bn"``
+    (BatchNorm2d) or ``"gn"``, every norm an ``nn.GroupNorm(gn_groups, C)`` under the same attribute name (no
+    buffers; ``gn_groups`` must divide every width; not together with ``se``)."""
 
     def __init__(self, block, layers, num_classes=1000, channels_last=True, drop_path_rate=0.0, drop_path_seed=0,
-                 zero_init_residual=False, se=False):
+                 zero_init_residual=False, se=False, norm="bn", gn_groups=32):
         super().__init__()
         if not 0.0 <= float(drop_path_rate) < 1.0:
             raise ValueError(f"drop_path_rate must be in [0, 1). Got: {drop_path_rate}")
+        if norm not in ("bn", "gn"):
+            raise ValueError(f"norm must be 'bn' or 'gn'. Got: {norm!r}")
+        self._norm = nn.BatchNorm2d
+        if norm == "gn":
+            if se:
+                raise ValueError("norm='gn' does not combine with se=True")
+            gn_groups = int(gn_groups)
+            # (every width is 64 * 2^k, times the block's expansion)
+            if gn_groups < 1 or 64 % gn_groups:
+                raise ValueError(f"gn_groups must divide every width (64 the narrowest). Got: {gn_groups}")
+            self._norm = functools.partial(nn.GroupNorm, gn_groups)
         install_load_hooks(self)  # loaded weights refresh the optimizer's prepared products
         self.inplanes = 64
         self._se = bool(se)
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
-        self.bn1 = nn.BatchNorm2d(64)
+        self.bn1 = self._norm(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
         self.layer1 = self._make_layer(block, 64, layers[0])
@@ -187,7 +221,7 @@ class ResNet(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         if zero_init_residual:
@@ -258,9 +292,11 @@ class ResNet(nn.Module):
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(
                 nn.Conv2d(self.inplanes, planes * block.expansion, 1, stride, 0, bias=False),
-                nn.BatchNorm2d(planes * block.expansion),
+                self._norm(planes * block.expansion),
             )
         kw = {"se": True} if self._se else {}
+        if self._norm is not nn.BatchNorm2d:
+            kw["norm"] = self._norm
         layers = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
@@ -296,7 +332,8 @@ class ResNet(nn.Module):
                 m._cdp_wamax = wam[i] if wam is not None else None
                 m._cdp_wt = wts[i] if wts is not None else None
             try:
-                x = CF.conv_bn_act(x, self.conv1, self.bn1, relu=True)
+                stem = CF.conv_gn_act if isinstance(self.bn1, nn.GroupNorm) else CF.conv_bn_act
+                x = stem(x, self.conv1, self.bn1, relu=True)
                 x = CF.max_pool2d(x, 3, 2, 1)
                 x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
             finally:
@@ -349,3 +386,23 @@ def seresnet101(**kw):
 
 def seresnet152(**kw):
     return ResNet(Bottleneck, [3, 8, 36, 3], se=True, **kw)
+
+
+def resnet18_gn(**kw):
+    return ResNet(BasicBlock, [2, 2, 2, 2], norm="gn", **kw)
+
+
+def resnet34_gn(**kw):
+    return ResNet(BasicBlock, [3, 4, 6, 3], norm="gn", **kw)
+
+
+def resnet50_gn(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], norm="gn", **kw)
+
+
+def resnet101_gn(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], norm="gn", **kw)
+
+
+def resnet152_gn(**kw):
+    return ResNet(Bottleneck, [3, 8, 36, 3], norm="gn", **kw)

@@ -22,6 +22,9 @@ __all__ = [
     "GradSink",
     "conv_bn_act",
     "se_scale_act",
+    "conv2d",
+    "group_norm_act",
+    "conv_gn_act",
     "drop_path_scales",
     "linear",
     "cross_entropy",
@@ -394,6 +397,127 @@ def se_scale_act(u, residual, w1, b1, w2, b2, drop_scale=None):
     if drop_scale is not None:
         y = y * drop_scale.to(y.dtype).view(-1, 1, 1, 1)
     return F.relu(y + residual)
+
+
+# --------------------------------------------------------------------------- conv + GroupNorm + act
+class _Conv2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, stride, pad, w_amax, w_t):
+        C = _native.lib()
+        x_amax = _get_amax(x)
+        if x_amax is None:  # f16x2: measured once here for the forward and the weight gradient (else None)
+            x_amax = C.act_max(x)
+        y = C.conv2d_fwd(x, w, b, stride, pad, False, x_amax, w_amax)[0]
+        ctx.cfg = (stride, pad)
+        ctx.params = (w, b)
+        ctx.extra = (x_amax, w_amax, w_t)  # W and x are unchanged by backward
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, w = ctx.saved_tensors
+        stride, pad = ctx.cfg
+        wp, bp = ctx.params
+        x_amax, w_amax, w_t = ctx.extra
+        ctx.extra = None
+        nig = ctx.needs_input_grad
+        C = _native.lib()
+        g_amax = _get_amax(gout)  # the producer's (group_norm_act's dy), else each GEMM measures gout itself
+        if g_amax is None and nig[0] and nig[1]:
+            g_amax = C.act_max(gout)
+        dw = dx = db = None
+        if nig[1]:
+            dw = C.conv2d_wgrad(gout, x, list(w.shape), stride, pad, _slot(wp, True), False, g_amax, x_amax)
+        if nig[0]:
+            dx = C.conv2d_dgrad(gout, w, list(x.shape), stride, pad, None, g_amax, w_amax, w_t)
+        if bp is not None and nig[2]:
+            db = gout.sum((0, 2, 3))
+        return dx, dw, db, None, None, None, None
+
+
+def _int_pair(v) -> bool:
+    return isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, int) for e in v) and v[0] == v[1]
+
+
+def conv2d(x, conv):
+    """``conv(x)`` for an ``nn.Conv2d``: the implicit-GEMM forward, data-gradient and weight-gradient kernels
+    behind one autograd function, with the f16x2 operand scales taken from ``x``'s and the incoming gradient's
+    producers and from the module's ``_cdp_wamax`` / ``_cdp_wt`` (:func:`weight_prep`) when they are there;
+    ``dW`` goes straight into its arena slot. Grouped, dilated or non-square-stride convs and CPU tensors run
+    ``F.conv2d`` (a bias gradient is a torch reduction: the models' convs have none)."""
+    plain = (conv.groups == 1 and tuple(conv.dilation) == (1, 1) and _int_pair(conv.stride)
+             and _int_pair(conv.padding) and conv.padding_mode == "zeros")
+    if use_native(x) and plain and x.dim() == 4 and x.dtype == torch.float32:
+        return _Conv2d.apply(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0],
+                             getattr(conv, "_cdp_wamax", None), getattr(conv, "_cdp_wt", None))
+    return conv(x)
+
+
+class _GroupNormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, weight, bias, groups, eps, relu, residual, drop_scale):
+        out, stats, out_amax = _native.lib().gn_act_fwd(y, residual, weight, bias, groups, eps, relu, drop_scale)
+        ctx.cfg = (groups, relu)
+        ctx.params = (weight, bias)
+        # the ReLU routing is read from `out` itself (out > 0)
+        ctx.save_for_backward(y, out if relu else None, stats, weight, drop_scale)
+        _set_amax(out, out_amax)  # f16x2: the next block's GEMMs scale their operands from these slots
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        y, out, stats, weight, drop_scale = ctx.saved_tensors
+        groups, relu = ctx.cfg
+        wp, bp = ctx.params
+        nig = ctx.needs_input_grad
+        dy, dr, dgamma, dbeta, dy_amax = _native.lib().gn_act_bwd(
+            gout, y, out, stats, weight, groups, relu, drop_scale, nig[6], _slot(wp, nig[1]), _slot(bp, nig[2]))
+        _set_amax(dy, dy_amax)  # f16x2: the conv's two gradient GEMMs scale dy from these slots
+        return (dy if nig[0] else None, dgamma if nig[1] else None, dbeta if nig[2] else None, None, None, None,
+                dr if nig[6] else None, None)
+
+
+def _gn_native(y, weight, bias, num_groups) -> bool:
+    """The shapes gn.hip takes: whole channel quads per group, or 1 or 2 channels per group."""
+    if not (use_native(y) and y.dim() == 4 and y.dtype == torch.float32 and weight is not None and bias is not None):
+        return False
+    C = y.shape[1]
+    if C % 4 or C > 2048 or C % num_groups or y.numel() >= 2 ** 31 or y.numel() == 0:
+        return False
+    return (C // num_groups) % 4 == 0 or C // num_groups <= 2
+
+
+def group_norm_act(y, weight, bias, num_groups, eps=1e-5, relu=True, residual=None, drop_scale=None):
+    """``act(s * group_norm(y, num_groups, weight, bias, eps) + residual)``: GroupNorm (statistics per image and
+    group, torch's formula) with the rest of a residual block's tail. ``residual`` is optional; ``drop_scale``
+    (stochastic depth, with a residual only) is fp32 ``[N]`` and multiplies image ``b``'s normalised branch before
+    the residual add; it gets no gradient.
+
+    float32 GPU tensors with ``C % 4 == 0``, ``C <= 2048`` and ``C / num_groups`` a multiple of 4, or 1 or 2, run
+    the HIP kernels (csrc/kernels/gn.hip: statistics and one NHWC pass forward; reduce, parameter gradients and
+    one NHWC pass backward). Anything else -- a group that straddles a channel quad, CPU tensors, float64,
+    ``CDP_FORCE_REFERENCE`` -- runs this PyTorch composition."""
+    if drop_scale is not None and residual is None:
+        raise ValueError("group_norm_act: drop_scale scales the branch of a residual block: it needs a residual")
+    if _gn_native(y, weight, bias, num_groups):
+        return _GroupNormAct.apply(y, weight, bias, int(num_groups), float(eps), bool(relu), residual, drop_scale)
+    out = F.group_norm(y, num_groups, weight, bias, eps)
+    if drop_scale is not None:
+        out = out * drop_scale.to(out.dtype).view(-1, 1, 1, 1)
+    if residual is not None:
+        out = out + residual
+    return F.relu(out) if relu else out
+
+
+def conv_gn_act(x, conv, gn, relu: bool = True, residual=None, drop_scale=None):
+    """``act(s * gn(conv(x)) + residual)`` for an ``nn.Conv2d`` / ``nn.GroupNorm`` pair: :func:`conv2d` then
+    :func:`group_norm_act` (GroupNorm's statistics are per image, so they cannot ride in the conv GEMM's epilogue
+    the way BatchNorm's per-channel ones do). ``residual`` / ``drop_scale`` as in :func:`conv_bn_act`."""
+    if drop_scale is not None and residual is None:
+        raise ValueError("conv_gn_act: drop_scale scales the branch of a residual block: it needs a residual")
+    return group_norm_act(conv2d(x, conv), gn.weight, gn.bias, gn.num_groups, gn.eps, relu=relu, residual=residual,
+                          drop_scale=drop_scale)
 
 
 # --------------------------------------------------------------------------- stochastic depth

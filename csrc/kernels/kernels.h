@@ -342,6 +342,29 @@ void se_bwd_apply_launch(const float* gout, const float* out, const float* g, co
                          const float* drop_scale, float* du, float* dr, int N, int HW, int C, SeSplit sp,
                          hipStream_t st);
 
+// gn.hip: GroupNorm fused with a residual block's tail, out = act(s[n] ((y - mean) rstd gamma + beta) + r) with
+// the statistics of (image, group) over Cg * HW values; y, r, out NHWC [N][HW][C], C % 4 == 0, C <= kMaxGnC,
+// Cg = C / G a multiple of 4, or 1 or 2. The NHWC kernels run one workgroup per (image, pixel chunk) of an
+// SeSplit (se_split: reduce = true for the two reductions, false for the two passes).
+constexpr int kMaxGnC = 2048;  // = kMaxActC (act_max.h)
+// part[N][sp.nchunk][2][C]: mean and M2 of every channel over the chunk's pixels
+void gn_stats_launch(const float* y, int N, int HW, int C, SeSplit sp, float* part, hipStream_t st);
+// rs: the split `part` was written with. Writes stats[N][G][2] = (mean, rstd) and out; r, drop_scale (fp32 [N],
+// with r only) may be nullptr; am: out's act max (ActMaxOut)
+void gn_apply_launch(const float* y, const float* r, const float* gamma, const float* beta, const float* drop_scale,
+                     const float* part, SeSplit rs, float* stats, float* out, int N, int HW, int C, int G, float eps,
+                     bool relu, SeSplit sp, ActMaxOut am, hipStream_t st);
+// part[N][sp.nchunk][2][C] = s1, s2 of the chunk; out == nullptr: no ReLU to route through
+void gn_bwd_reduce_launch(const float* gout, const float* out, const float* y, const float* stats,
+                          const float* drop_scale, int N, int HW, int C, int G, SeSplit sp, float* part,
+                          hipStream_t st);
+// dbeta / dgamma [C] = plane 0 / 1 of part summed over its `rows` (image, chunk) rows
+void gn_param_grad_launch(const float* part, int rows, int C, float* dgamma, float* dbeta, hipStream_t st);
+// rchunk: the chunks per image of `part`; dr == nullptr: not wanted; am: dy's act max
+void gn_bwd_apply_launch(const float* gout, const float* out, const float* y, const float* stats, const float* gamma,
+                         const float* drop_scale, const float* part, int rchunk, float* dy, float* dr, int N, int HW,
+                         int C, int G, SeSplit sp, ActMaxOut am, hipStream_t st);
+
 // misc.hip
 // eps: label smoothing in [0, 1] (target distribution (1 - eps) onehot + eps / C; 0: the plain kernels'
 // arithmetic); topk >= 1: a row counts as correct when fewer than topk logits rank above its target's

@@ -290,6 +290,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("h"), py::arg("g"), py::arg("w1"), py::arg("w2"), py::arg("drop_scale"), py::arg("need_dr"),
         py::arg("dw1_out") = py::none(), py::arg("db1_out") = py::none(), py::arg("dw2_out") = py::none(),
         py::arg("db2_out") = py::none(), "(du, dr, dw1, db1, dw2, db2) of se_scale_act_fwd");
+  m.def("gn_act_fwd", &gn_act_fwd, py::arg("y"), py::arg("residual"), py::arg("gamma"), py::arg("beta"),
+        py::arg("groups"), py::arg("eps"), py::arg("relu"), py::arg("drop_scale") = py::none(),
+        "GroupNorm block tail: (out, stats, out's act max) with out = act(s (group_norm(y) gamma + beta) + residual)");
+  m.def("gn_act_bwd", &gn_act_bwd, py::arg("gout"), py::arg("y"), py::arg("out"), py::arg("stats"), py::arg("gamma"),
+        py::arg("groups"), py::arg("relu"), py::arg("drop_scale"), py::arg("need_dr"),
+        py::arg("dgamma_out") = py::none(), py::arg("dbeta_out") = py::none(),
+        "(dy, dr, dgamma, dbeta, dy's act max) of gn_act_fwd");
 
   // -------------------------------------------------------------- RCCL
   py::class_<RcclWork, std::shared_ptr<RcclWork>>(m, "RcclWork")

@@ -3078,11 +3078,12 @@ at::Tensor se_bias(const at::Tensor& b, int64_t O, const char* name) {
   return b.contiguous();
 }
 // a parameter gradient's destination: the given arena slot (shaped like the parameter), else a new tensor
-at::Tensor se_grad_dst(const c10::optional<at::Tensor>& slot, const at::Tensor& like, const char* name) {
+at::Tensor se_grad_dst(const c10::optional<at::Tensor>& slot, const at::Tensor& like, const char* name,
+                       const char* op = "se_scale_act_bwd") {
   if (!slot.has_value() || !slot->defined()) return at::empty_like(like);
   TORCH_CHECK(slot->is_cuda() && slot->scalar_type() == at::kFloat && slot->numel() == like.numel() &&
                   slot->is_non_overlapping_and_dense(),
-              "se_scale_act_bwd: the ", name, " slot must be a dense float32 tensor of the parameter's size");
+              op, ": the ", name, " slot must be a dense float32 tensor of the parameter's size");
   return *slot;
 }
 struct SeDims {
@@ -3182,6 +3183,114 @@ std::vector<at::Tensor> se_scale_act_bwd(const at::Tensor& gout_, const at::Tens
   se_bwd_apply_launch(gout.data_ptr<float>(), out.data_ptr<float>(), g.data_ptr<float>(), dpool.data_ptr<float>(),
                       dsp, du.data_ptr<float>(), need_dr ? dr.data_ptr<float>() : nullptr, d.N, d.HW, d.C, ps, st);
   return {du, dr, dw1, db1, dw2, db2};
+}
+
+// ---------------------------------------------------------------- GroupNorm (gn.hip)
+namespace {
+struct GnDims {
+  int N, C, H, W, HW, G;
+};
+GnDims gn_dims(const at::Tensor& y, const at::Tensor& gamma, int64_t groups, const char* op) {
+  TORCH_CHECK(y.dim() == 4, op, ": y must be [N, C, H, W]");
+  const int64_t N = y.size(0), C = y.size(1), H = y.size(2), W = y.size(3);
+  TORCH_CHECK(N > 0 && H * W > 0, op, ": empty input");
+  TORCH_CHECK(C % 4 == 0 && C <= kMaxGnC, op, ": needs C % 4 == 0 and C <= ", kMaxGnC, ", got C = ", C);
+  TORCH_CHECK(groups >= 1 && C % groups == 0, op, ": groups = ", groups, " must divide C = ", C);
+  const int64_t Cg = C / groups;
+  TORCH_CHECK(Cg % 4 == 0 || Cg <= 2, op, ": channels per group must be a multiple of 4, or 1 or 2 (a group may not ",
+              "straddle a channel quad), got ", Cg);
+  TORCH_CHECK(N * H * W * C < (1LL << 31), op, ": N * H * W * C = ", N * H * W * C,
+              " does not fit the kernels' 32-bit pixel indexing (must be < 2^31)");
+  check_f32_cuda(gamma, "gamma");
+  TORCH_CHECK(gamma.dim() == 1 && gamma.size(0) == C && gamma.is_contiguous(), op, ": gamma must be a contiguous [",
+              C, "] tensor");
+  return {(int)N, (int)C, (int)H, (int)W, (int)(H * W), (int)groups};
+}
+// a fresh act max for `t` under the f16x2 engine (else undefined, and no maxima are published)
+ActMaxOut gn_act_max(at::Tensor& slots, const GnDims& d, const at::Tensor& t, hipStream_t st) {
+  if (!f16x2_mode()) return ActMaxOut{nullptr, nullptr};
+  slots = new_act_max(d.N, d.C, t, st);
+  return act_out(slots, d.N);
+}
+}  // namespace
+
+// {out, stats [N, G, 2] = (mean, rstd), out's act max (f16x2 engine, else undefined)}
+std::vector<at::Tensor> gn_act_fwd(const at::Tensor& y_, const c10::optional<at::Tensor>& residual,
+                                   const at::Tensor& gamma, const at::Tensor& beta, int64_t groups, double eps,
+                                   bool relu, const c10::optional<at::Tensor>& drop_scale) {
+  check_f32_cuda(y_, "y");
+  const GnDims d = gn_dims(y_, gamma, groups, "gn_act_fwd");
+  check_f32_cuda(beta, "beta");
+  TORCH_CHECK(beta.dim() == 1 && beta.size(0) == d.C && beta.is_contiguous(), "gn_act_fwd: beta must be a contiguous [",
+              d.C, "] tensor");
+  const bool has_res = residual.has_value() && residual->defined();
+  const at::Tensor y = nhwc(y_);
+  at::Tensor r;
+  if (has_res) {
+    check_f32_cuda(*residual, "residual");
+    TORCH_CHECK(residual->sizes() == y_.sizes(), "gn_act_fwd: the residual must have y's shape");
+    r = nhwc(*residual);
+  }
+  const float* dsp = drop_scale_ptr(drop_scale, y, "gn_act_fwd");
+  TORCH_CHECK(!dsp || has_res, "gn_act_fwd: drop_scale scales the branch of a residual block: it needs a residual");
+  hipStream_t st = cur_stream();
+  auto opts = y.options();
+  const SeSplit rs = se_split(d.N, d.HW, d.C, true, num_cus()), ps = se_split(d.N, d.HW, d.C, false, num_cus());
+  at::Tensor part = at::empty({d.N, rs.nchunk, 2, d.C}, opts);
+  at::Tensor stats = at::empty({d.N, d.G, 2}, opts);
+  at::Tensor out = at::empty({d.N, d.C, d.H, d.W}, opts.memory_format(at::MemoryFormat::ChannelsLast));
+  gn_stats_launch(y.data_ptr<float>(), d.N, d.HW, d.C, rs, part.data_ptr<float>(), st);
+  at::Tensor out_amax;  // the output's act max: the next block's operand scales (f16x2)
+  const ActMaxOut am = gn_act_max(out_amax, d, out, st);
+  gn_apply_launch(y.data_ptr<float>(), has_res ? r.data_ptr<float>() : nullptr, gamma.data_ptr<float>(),
+                  beta.data_ptr<float>(), dsp, part.data_ptr<float>(), rs, stats.data_ptr<float>(),
+                  out.data_ptr<float>(), d.N, d.HW, d.C, d.G, (float)eps, relu, ps, am, st);
+  return {out, stats, out_amax};
+}
+
+// {dy, dr (undefined when !need_dr), dgamma, dbeta, dy's act max}; the parameter gradients are written into the
+// given slots or into new tensors. `out` is read for the ReLU routing only (relu).
+std::vector<at::Tensor> gn_act_bwd(const at::Tensor& gout_, const at::Tensor& y_, const c10::optional<at::Tensor>& out_,
+                                   const at::Tensor& stats, const at::Tensor& gamma, int64_t groups, bool relu,
+                                   const c10::optional<at::Tensor>& drop_scale, bool need_dr,
+                                   const c10::optional<at::Tensor>& dgamma_out,
+                                   const c10::optional<at::Tensor>& dbeta_out) {
+  check_f32_cuda(gout_, "grad_output");
+  check_f32_cuda(y_, "y");
+  const GnDims d = gn_dims(y_, gamma, groups, "gn_act_bwd");
+  TORCH_CHECK(gout_.sizes() == y_.sizes(), "gn_act_bwd: grad_output must have y's shape");
+  const at::Tensor gout = nhwc(gout_), y = nhwc(y_);
+  at::Tensor out;
+  if (relu) {
+    TORCH_CHECK(out_.has_value() && out_->defined(), "gn_act_bwd: the ReLU routing needs the forward's out");
+    check_f32_cuda(*out_, "out");
+    TORCH_CHECK(out_->sizes() == y_.sizes(), "gn_act_bwd: out must have y's shape");
+    out = nhwc(*out_);
+  }
+  check_f32_cuda(stats, "stats");
+  TORCH_CHECK(stats.is_contiguous() && stats.numel() == (int64_t)d.N * d.G * 2,
+              "gn_act_bwd: stats must be the forward's contiguous [N, G, 2] block");
+  const float* dsp = drop_scale_ptr(drop_scale, y, "gn_act_bwd");
+  hipStream_t st = cur_stream();
+  auto opts = y.options();
+  const SeSplit rs = se_split(d.N, d.HW, d.C, true, num_cus()), ps = se_split(d.N, d.HW, d.C, false, num_cus());
+  at::Tensor part = at::empty({d.N, rs.nchunk, 2, d.C}, opts);
+  at::Tensor dgamma = se_grad_dst(dgamma_out, gamma, "dgamma", "gn_act_bwd");
+  at::Tensor dbeta = se_grad_dst(dbeta_out, gamma, "dbeta", "gn_act_bwd");
+  auto nhwc_opts = opts.memory_format(at::MemoryFormat::ChannelsLast);
+  at::Tensor dy = at::empty({d.N, d.C, d.H, d.W}, nhwc_opts);
+  at::Tensor dr = need_dr ? at::empty({d.N, d.C, d.H, d.W}, nhwc_opts) : at::Tensor();
+  const float* outp = relu ? out.data_ptr<float>() : nullptr;
+  gn_bwd_reduce_launch(gout.data_ptr<float>(), outp, y.data_ptr<float>(), stats.data_ptr<float>(), dsp, d.N, d.HW, d.C,
+                       d.G, rs, part.data_ptr<float>(), st);
+  gn_param_grad_launch(part.data_ptr<float>(), d.N * rs.nchunk, d.C, dgamma.data_ptr<float>(),
+                       dbeta.data_ptr<float>(), st);
+  at::Tensor dy_amax;  // dy's act max: operand scales of the conv's two gradient GEMMs (f16x2)
+  const ActMaxOut am = gn_act_max(dy_amax, d, dy, st);
+  gn_bwd_apply_launch(gout.data_ptr<float>(), outp, y.data_ptr<float>(), stats.data_ptr<float>(),
+                      gamma.data_ptr<float>(), dsp, part.data_ptr<float>(), rs.nchunk, dy.data_ptr<float>(),
+                      need_dr ? dr.data_ptr<float>() : nullptr, d.N, d.HW, d.C, d.G, ps, am, st);
+  return {dy, dr, dgamma, dbeta, dy_amax};
 }
 
 

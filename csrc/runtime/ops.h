@@ -273,6 +273,18 @@ std::vector<at::Tensor> se_scale_act_bwd(const at::Tensor& gout, const at::Tenso
                                          const c10::optional<at::Tensor>& db1_out,
                                          const c10::optional<at::Tensor>& dw2_out,
                                          const c10::optional<at::Tensor>& db2_out);
+// GroupNorm fused with a residual block's tail (gn.hip): out = act(s[n] (group_norm(y) gamma + beta) + residual),
+// the statistics of (image, group) over C / groups * H * W values; residual and drop_scale (with a residual only)
+// are optional. {out, stats [N, G, 2] = (mean, rstd), out's act max (f16x2 engine)}
+std::vector<at::Tensor> gn_act_fwd(const at::Tensor& y, const c10::optional<at::Tensor>& residual,
+                                   const at::Tensor& gamma, const at::Tensor& beta, int64_t groups, double eps,
+                                   bool relu, const c10::optional<at::Tensor>& drop_scale);
+// {dy, dr (need_dr), dgamma, dbeta, dy's act max}; the *_out slots receive the parameter gradients in place
+std::vector<at::Tensor> gn_act_bwd(const at::Tensor& gout, const at::Tensor& y, const c10::optional<at::Tensor>& out,
+                                   const at::Tensor& stats, const at::Tensor& gamma, int64_t groups, bool relu,
+                                   const c10::optional<at::Tensor>& drop_scale, bool need_dr,
+                                   const c10::optional<at::Tensor>& dgamma_out,
+                                   const c10::optional<at::Tensor>& dbeta_out);
 
 // CDP_GEMM_LOG=1: the GEMM launches so far as (kind, M, N, K, bm, bn, splits), in enqueue order
 std::vector<std::tuple<std::string, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>> gemm_log(bool clear);
