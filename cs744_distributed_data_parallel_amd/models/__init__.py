@@ -1,7 +1,8 @@
 """Model zoo: the reference's VGG family (CIFAR-shaped) and the ResNet family (ImageNet-shaped)."""
 from .resnet import (ResNet, SEModule, resnet18, resnet18_gn, resnet34, resnet34_gn, resnet50, resnet50_gn, resnet101,
                      resnet101_gn, resnet152, resnet152_gn, seresnet18, seresnet34, seresnet50, seresnet101,
-                     seresnet152)
+                     seresnet152, resnext50_32x4d, resnext101_32x8d, resnext101_64x4d, seresnext50_32x4d,
+                     wide_resnet50_2, wide_resnet101_2)
 from .vgg import VGG, VGG11, VGG13, VGG16, VGG19, cfg, make_layers
 
 _REGISTRY = {
@@ -28,6 +29,15 @@ _REGISTRY = {
 }
 # the Squeeze-and-Excitation models under their "resnetNN_se" spelling too (get_model strips "_" and "-")
 _REGISTRY.update({"resnet" + k[len("seresnet"):] + "se": v for k, v in list(_REGISTRY.items()) if k.startswith("seresnet")})
+# cardinality and width: a grouped 3x3 conv2 (ResNeXt) or a doubled one (Wide ResNet) in every Bottleneck
+_REGISTRY.update({
+    "resnext5032x4d": resnext50_32x4d,
+    "resnext10132x8d": resnext101_32x8d,
+    "resnext10164x4d": resnext101_64x4d,
+    "seresnext5032x4d": seresnext50_32x4d,
+    "wideresnet502": wide_resnet50_2,
+    "wideresnet1012": wide_resnet101_2,
+})
 
 # input shape (C, H, W) and number of classes per family
 INPUT_SHAPES = {k: ((3, 32, 32), 10) if k.startswith("vgg") else ((3, 224, 224), 1000) for k in _REGISTRY}
@@ -49,5 +59,7 @@ __all__ = [
     "ResNet", "resnet18", "resnet34", "resnet50", "resnet101", "resnet152",
     "resnet18_gn", "resnet34_gn", "resnet50_gn", "resnet101_gn", "resnet152_gn",
     "SEModule", "seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152",
+    "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "seresnext50_32x4d", "wide_resnet50_2",
+    "wide_resnet101_2",
     "get_model", "list_models", "INPUT_SHAPES",
 ]

@@ -27,6 +27,11 @@ GroupNorm (``norm="gn"``, the ``resnetNN_gn`` factories; torchvision's ``norm_la
 ``state_dict()`` is ``resnetNN``'s minus the running statistics. Its statistics are per image: no buffers, nothing
 that depends on how a batch is cut across ranks. Every ``conv -> GN [-> +shortcut] [-> ReLU]`` is
 ``CF.conv_gn_act`` (csrc/kernels/gn.hip); the shortcut's two gradients meet in an autograd add.
+
+ResNeXt / Wide ResNet (``groups`` / ``width_per_group``, the ``resnextNN_GxWd`` and ``wide_resnetNN_2`` factories;
+torchvision's rule and ``state_dict()``): the Bottleneck's ``conv2`` is a grouped 3x3 conv of
+``int(planes * width_per_group / 64) * groups`` channels, which the same fused ``conv_bn_act`` runs on the direct
+grouped kernels (csrc/kernels/gconv.hip) when ``groups > 1``.
 """
 from __future__ import annotations
 
@@ -82,8 +87,11 @@ class BasicBlock(nn.Module):
     expansion = 1
     _drop_scale = None
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False, norm=nn.BatchNorm2d):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False, norm=nn.BatchNorm2d, groups=1,
+                 base_width=64):
         super().__init__()
+        if groups != 1 or base_width != 64:
+            raise ValueError("BasicBlock only supports groups=1 and base_width=64")
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = norm(planes)
         self.relu = nn.ReLU(inplace=True)
@@ -127,12 +135,14 @@ class Bottleneck(nn.Module):
     expansion = 4
     _drop_scale = None
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False, norm=nn.BatchNorm2d):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, se=False, norm=nn.BatchNorm2d, groups=1,
+                 base_width=64):
         super().__init__()
-        width = planes
+        width = int(planes * (base_width / 64.0)) * groups  # torchvision's rule (ResNeXt / Wide ResNet)
         self.conv1 = nn.Conv2d(inplanes, width, 1, 1, 0, bias=False)
         self.bn1 = norm(width)
-        self.conv2 = nn.Conv2d(width, width, 3, stride, 1, bias=False)
+        # groups > 1: the direct grouped kernels (csrc/kernels/gconv.hip) inside the same fused block
+        self.conv2 = nn.Conv2d(width, width, 3, stride, 1, groups=groups, bias=False)
         self.bn2 = norm(width)
         self.conv3 = nn.Conv2d(width, planes * 4, 1, 1, 0, bias=False)
         self.bn3 = norm(planes * 4)
@@ -187,11 +197,18 @@ class ResNet(nn.Module):
     (torchvision's rule), so every block starts as its shortcut. ``se``: every block carries an
     :class:`SEModule` (``layerL.B.se.fc1`` / ``fc2``) and gates its branch with it. ``norm``: ``"bn"``
     (BatchNorm2d) or ``"gn"``, every norm an ``nn.GroupNorm(gn_groups, C)`` under the same attribute name (no
-    buffers; ``gn_groups`` must divide every width; not together with ``se``)."""
+    buffers; ``gn_groups`` must divide every width; not together with ``se``). ``groups`` / ``width_per_group``
+    (Bottleneck only): torchvision's cardinality and width, ``conv2`` a grouped 3x3 of ``int(planes *
+    width_per_group / 64) * groups`` channels (ResNeXt: ``groups=32``; Wide ResNet: ``width_per_group=128``)."""
 
     def __init__(self, block, layers, num_classes=1000, channels_last=True, drop_path_rate=0.0, drop_path_seed=0,
-                 zero_init_residual=False, se=False, norm="bn", gn_groups=32):
+                 zero_init_residual=False, se=False, norm="bn", gn_groups=32, groups=1, width_per_group=64):
         super().__init__()
+        if block is BasicBlock and (groups != 1 or width_per_group != 64):
+            raise ValueError("BasicBlock only supports groups=1 and width_per_group=64")
+        if int(groups) < 1 or int(width_per_group) < 1:
+            raise ValueError(f"groups and width_per_group must be positive. Got: {groups}, {width_per_group}")
+        self.groups, self.base_width = int(groups), int(width_per_group)
         if not 0.0 <= float(drop_path_rate) < 1.0:
             raise ValueError(f"drop_path_rate must be in [0, 1). Got: {drop_path_rate}")
         if norm not in ("bn", "gn"):
@@ -297,6 +314,8 @@ class ResNet(nn.Module):
         kw = {"se": True} if self._se else {}
         if self._norm is not nn.BatchNorm2d:
             kw["norm"] = self._norm
+        if self.groups != 1 or self.base_width != 64:
+            kw.update(groups=self.groups, base_width=self.base_width)
         layers = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
@@ -324,8 +343,11 @@ class ResNet(nn.Module):
             # (stride-1 convs; the stem's input needs no gradient, stride-2 convs use sub-filters);
             # each conv module holds its entries for the duration of this forward (conv_bn_act
             # reads them)
-            # (an SE block's fc1 / fc2 feed no GEMM: se_scale_act reads them as they are)
-            convs = [m for n, m in self.named_modules() if isinstance(m, nn.Conv2d) and ".se." not in n]
+            # (an SE block's fc1 / fc2 feed no GEMM: se_scale_act reads them as they are; neither does a grouped
+            # conv's weight: the direct kernels read it unscaled and untransposed, so it is left out of the list
+            # and of the optimizer's fused weight preparation that follows it)
+            convs = [m for n, m in self.named_modules()
+                     if isinstance(m, nn.Conv2d) and ".se." not in n and m.groups == 1]
             need = [m.stride[0] == 1 and (m is not self.conv1 or x.requires_grad) for m in convs]
             wam, wts = CF.weight_prep([m.weight for m in convs], need)
             for i, m in enumerate(convs):
@@ -406,3 +428,27 @@ def resnet101_gn(**kw):
 
 def resnet152_gn(**kw):
     return ResNet(Bottleneck, [3, 8, 36, 3], norm="gn", **kw)
+
+
+def resnext50_32x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], groups=32, width_per_group=4, **kw)
+
+
+def resnext101_32x8d(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], groups=32, width_per_group=8, **kw)
+
+
+def resnext101_64x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], groups=64, width_per_group=4, **kw)
+
+
+def seresnext50_32x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], groups=32, width_per_group=4, se=True, **kw)
+
+
+def wide_resnet50_2(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], width_per_group=128, **kw)
+
+
+def wide_resnet101_2(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], width_per_group=128, **kw)

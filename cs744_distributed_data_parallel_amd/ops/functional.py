@@ -174,7 +174,7 @@ class _ConvBNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, rm, rv, nbt, momentum, eps, training, stride, pad, pool, relu, residual,
                 res_sink=None, dx_sink=None, w_amax=None, w_t=None, bn_link=False, defer_apply=False,
-                drop_scale=None):
+                drop_scale=None, groups=1):
         C = _native.lib()
         # a residual that is a deferred BatchNorm branch (defer_apply below): its raw conv output and
         # stats go to this block's apply pass instead of the (never written) placeholder
@@ -182,10 +182,11 @@ class _ConvBNAct(torch.autograd.Function):
         out, y, stats, xsave, out_amax, x_amax, w_amax, rmask = C.conv_bn_act_fwd(
             x, w, b, gamma, beta, rm, rv, nbt, momentum, eps, training, stride, pad, pool, relu,
             residual if lazy is None else None, _get_amax(x), w_amax,
-            None if lazy is None else lazy[0], None if lazy is None else lazy[1], defer_apply, drop_scale,
+            None if lazy is None else lazy[0], None if lazy is None else lazy[1], defer_apply, drop_scale, groups,
         )
         if defer_apply:  # statistics only: `out` is a shape-only placeholder nothing may read
             out._cdp_deferred_bn = (y, stats, out._version)
+        ctx.groups = groups
         ctx.cfg = (stride, pad, pool, relu, training, b is not None, residual is not None)
         ctx.params = (w, b, gamma, beta)
         ctx.sinks = (res_sink, dx_sink)
@@ -197,7 +198,7 @@ class _ConvBNAct(torch.autograd.Function):
         ctx.save_for_backward(xsave, w, y, stats, zout, drop_scale)  # xsave: x, or x zero-padded to 4k channels
         _set_amax(out, out_amax)
         # the producer of x handed over its BN (see _BNLink) if this block is its only consumer
-        ctx.link_in = _get_link(x) if dx_sink is None else None
+        ctx.link_in = _get_link(x) if (dx_sink is None and groups == 1) else None
         if ctx.link_in is not None:
             ctx.link_in.consumers += 1
         ctx.link_out = None
@@ -236,7 +237,7 @@ class _ConvBNAct(torch.autograd.Function):
         dx, dw, db, dgamma, dbeta, dres, prev_part, _ = C.conv_bn_act_bwd(
             gout, x, w, y, stats, stride, pad, pool, relu, nig[0], has_bias, zout, training,
             _slot(wp, nig[1]), _slot(bp, nig[2] and has_bias), _slot(gp, nig[3]), _slot(betap, nig[4]), addend,
-            *ctx.amax, ctx.w_t, part_in, *prev, bp, drop_scale,
+            *ctx.amax, ctx.w_t, part_in, *prev, bp, drop_scale, ctx.groups,
         )
         ctx.w_t = None
         if li is not None:
@@ -260,7 +261,7 @@ class _ConvBNAct(torch.autograd.Function):
             dbeta if ctx.needs_input_grad[4] else None,
             None, None, None, None, None, None, None, None, None, None,
             dres if has_res else None,
-            None, None, None, None, None, None, None,
+            None, None, None, None, None, None, None, None,
         )
 
 
@@ -299,12 +300,26 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
     ``drop_scale`` (stochastic depth; needs ``residual``, no ``pool`` / ``defer_apply``): fp32 ``[N]``, image
     ``b``'s BatchNorm output is multiplied by ``drop_scale[b]`` before the residual add, inside the same apply
     pass; the BatchNorm statistics and the residual are untouched. It gets no gradient.
+    A grouped ``conv`` (``conv.groups > 1``: 3x3, pad 1, stride 1 or 2, channels per group multiples of 4 and
+    ``<= 64``) runs the direct fp32 kernels of csrc/kernels/gconv.hip inside the same block; it takes none of the
+    options above but ``relu`` (``ValueError`` otherwise).
     """
     if drop_scale is not None and (residual is None or pool or defer_apply):
         raise ValueError("conv_bn_act: drop_scale scales the branch of a residual block: it needs a residual and "
                          "takes neither pool nor defer_apply")
     stride = conv.stride[0]
     pad = conv.padding[0]
+    groups = int(conv.groups)
+    if groups > 1 and use_native(x):
+        # the direct grouped kernels (csrc/kernels/gconv.hip) serve a plain conv -> BN -> act
+        if (residual is not None or pool or defer_apply or drop_scale is not None or res_sink is not None
+                or dx_sink is not None or bn_link):
+            raise ValueError("conv_bn_act: a grouped conv takes no residual, pool, defer_apply, drop_scale, "
+                             "res_sink / dx_sink or bn_link")
+        if not _gconv_native(x, conv):
+            raise ValueError("conv_bn_act: a grouped conv must be 3x3 / pad 1 / stride 1 or 2 / dilation 1 with "
+                             f"channels per group multiples of 4 and <= 64. Got: {conv}")
+        w_amax = w_t = None  # a grouped weight's products are never a dense GEMM's operands
     if use_native(x):
         training = bn.training or not bn.track_running_stats
         track = bn.track_running_stats and bn.training
@@ -327,13 +342,14 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
             residual,
             res_sink,
             dx_sink,
-            w_amax if w_amax is not None else getattr(conv, "_cdp_wamax", None),
-            w_t if w_t is not None else getattr(conv, "_cdp_wt", None),
+            None if groups > 1 else (w_amax if w_amax is not None else getattr(conv, "_cdp_wamax", None)),
+            None if groups > 1 else (w_t if w_t is not None else getattr(conv, "_cdp_wt", None)),
             bn_link,
             defer_apply,
             drop_scale,
+            groups,
         )
-    y = F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding)
+    y = F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, groups=conv.groups)
     y = bn(y)
     if drop_scale is not None:
         y = y * drop_scale.to(y.dtype).view(-1, 1, 1, 1)
@@ -436,21 +452,68 @@ class _Conv2d(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+class _GConv2d(torch.autograd.Function):
+    """A grouped 3x3 conv over the three direct fp32 kernels (csrc/kernels/gconv.hip); no operand scales."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, groups):
+        y = _native.lib().gconv2d_fwd(x, w, b, stride, 1, groups, False)[0]
+        ctx.cfg = (stride, groups)
+        ctx.params = (w, b)
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, w = ctx.saved_tensors
+        stride, groups = ctx.cfg
+        wp, bp = ctx.params
+        nig = ctx.needs_input_grad
+        C = _native.lib()
+        dw = dx = db = None
+        if nig[1]:
+            dw = C.gconv2d_wgrad(gout, x, list(w.shape), stride, 1, groups, _slot(wp, True), False)
+        if nig[0]:
+            dx = C.gconv2d_dgrad(gout, w, list(x.shape), stride, 1, groups, None)
+        if bp is not None and nig[2]:
+            db = gout.sum((0, 2, 3))
+        return dx, dw, db, None, None
+
+
 def _int_pair(v) -> bool:
     return isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, int) for e in v) and v[0] == v[1]
+
+
+def _gconv_native(x, conv) -> bool:
+    """The grouped kernels' domain: 3x3 / pad 1 / stride 1 or 2 / dilation 1, whole groups of 4k <= 64 channels on
+    both sides, float32 NCHW-shaped tensors below 2^31 elements."""
+    if not (conv.groups > 1 and x.dim() == 4 and x.dtype == torch.float32 and tuple(conv.kernel_size) == (3, 3)
+            and tuple(conv.dilation) == (1, 1) and tuple(conv.stride) in ((1, 1), (2, 2))
+            and tuple(conv.padding) == (1, 1) and conv.padding_mode == "zeros"):
+        return False
+    cgi, cgo = conv.in_channels // conv.groups, conv.out_channels // conv.groups
+    if cgi % 4 or cgo % 4 or cgi > 64 or cgo > 64 or x.shape[1] != conv.in_channels or x.numel() == 0:
+        return False
+    s = conv.stride[0]
+    out = x.shape[0] * conv.out_channels * ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1)
+    return x.numel() < 2 ** 31 and out < 2 ** 31
 
 
 def conv2d(x, conv):
     """``conv(x)`` for an ``nn.Conv2d``: the implicit-GEMM forward, data-gradient and weight-gradient kernels
     behind one autograd function, with the f16x2 operand scales taken from ``x``'s and the incoming gradient's
     producers and from the module's ``_cdp_wamax`` / ``_cdp_wt`` (:func:`weight_prep`) when they are there;
-    ``dW`` goes straight into its arena slot. Grouped, dilated or non-square-stride convs and CPU tensors run
-    ``F.conv2d`` (a bias gradient is a torch reduction: the models' convs have none)."""
+    ``dW`` goes straight into its arena slot. A grouped 3x3 conv (pad 1, stride 1 or 2, channels per group
+    multiples of 4 and <= 64) runs the direct fp32 kernels of csrc/kernels/gconv.hip the same way. Other grouped
+    convs (depthwise, 1x1, ...), dilated or non-square-stride convs and CPU tensors run ``F.conv2d`` (a bias
+    gradient is a torch reduction: the models' convs have none)."""
     plain = (conv.groups == 1 and tuple(conv.dilation) == (1, 1) and _int_pair(conv.stride)
              and _int_pair(conv.padding) and conv.padding_mode == "zeros")
     if use_native(x) and plain and x.dim() == 4 and x.dtype == torch.float32:
         return _Conv2d.apply(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0],
                              getattr(conv, "_cdp_wamax", None), getattr(conv, "_cdp_wt", None))
+    if use_native(x) and _gconv_native(x, conv):
+        return _GConv2d.apply(x, conv.weight, conv.bias, conv.stride[0], conv.groups)
     return conv(x)
 
 

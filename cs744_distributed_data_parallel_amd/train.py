@@ -190,8 +190,10 @@ def test_model(model, test_loader, criterion, print_fn=print, topk=None):
 
 
 def _is_resnet(name: str) -> bool:
-    """The ImageNet-shaped ResNet family, its Squeeze-and-Excitation models (``seresnetNN``) included."""
-    return name.lower().replace("-", "").replace("_", "").startswith(("resnet", "seresnet"))
+    """The ImageNet-shaped ResNet family, its Squeeze-and-Excitation (``seresnetNN``), ResNeXt (``resnextNN_GxWd``,
+    ``seresnext50_32x4d``) and Wide ResNet (``wide_resnetNN_2``) models included."""
+    return name.lower().replace("-", "").replace("_", "").startswith(
+        ("resnet", "seresnet", "resnext", "seresnext", "wideresnet"))
 
 
 def build_data(args, device, train: bool):

@@ -365,6 +365,32 @@ void gn_bwd_apply_launch(const float* gout, const float* out, const float* y, co
                          const float* drop_scale, const float* part, int rchunk, float* dy, float* dr, int N, int HW,
                          int C, int G, SeSplit sp, ActMaxOut am, hipStream_t st);
 
+// gconv.hip: direct grouped 3x3 convolution (pad 1, stride 1 or 2) in fp32 FMA; cgi / cgo = channels per group
+// of the input / output, multiples of 4 and <= 64; every index of src and dst below 2^31.
+constexpr int kGconvRows = 64;  // rows of a workgroup's tile = rows per BatchNorm partial
+struct GConvParams {
+  const float* src;     // forward: x NHWC [N][SH][SW][G cgi]; data gradient: dY [N][SH][SW][G cgo]
+  const float* w;       // [G cgo][3][3][cgi]
+  float* dst;           // rows (n, oh, ow): forward y [M][G cgo]; data gradient dX [M][G cgi]
+  const float* bias;    // [G cgo] or nullptr (forward)
+  const float* addend;  // optional: dst += addend (dst's layout; may alias dst)
+  float* part;          // forward: BN partials [ceil(M / kGconvRows)][G cgo][2] (mean, M2) or nullptr
+  int N, SH, SW, OH, OW, G, cgi, cgo, stride, M;
+};
+void gconv_fwd_launch(const GConvParams& p, hipStream_t st);
+void gconv_dgrad_launch(const GConvParams& p, hipStream_t st);
+struct GConvWgradParams {
+  const float* dy;  // [M][G cgo], rows (n, p, q)
+  const float* x;   // NHWC [N][H][W][G cgi]
+  float* slab;      // [S][G cgo][3][3][cgi]
+  int N, H, W, P, Q, G, cgi, cgo, stride, M, tiles_per_chunk;
+};
+struct GConvChunks {
+  int S, tiles_per_chunk;
+};
+GConvChunks gconv_wgrad_chunks(long long M, int G, int cgi, int cgo, int cus);
+void gconv_wgrad_launch(const GConvWgradParams& p, int S, hipStream_t st);
+
 // misc.hip
 // eps: label smoothing in [0, 1] (target distribution (1 - eps) onehot + eps / C; 0: the plain kernels'
 // arithmetic); topk >= 1: a row counts as correct when fewer than topk logits rank above its target's

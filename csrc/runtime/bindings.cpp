@@ -51,12 +51,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv2d_wgrad", &conv2d_wgrad, py::arg("dy"), py::arg("x"), py::arg("w_shape"), py::arg("stride"),
         py::arg("pad"), py::arg("out") = py::none(), py::arg("accumulate") = false, py::arg("dy_amax") = py::none(),
         py::arg("x_amax") = py::none());
+  m.def("gconv2d_fwd", &gconv2d_fwd, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("stride"), py::arg("pad"),
+        py::arg("groups"), py::arg("want_stats") = false,
+        "grouped 3x3 conv forward by the direct fp32 kernels; (y[, BN partials, rows per partial])");
+  m.def("gconv2d_dgrad", &gconv2d_dgrad, py::arg("dy"), py::arg("w"), py::arg("in_shape"), py::arg("stride"),
+        py::arg("pad"), py::arg("groups"), py::arg("addend") = py::none());
+  m.def("gconv2d_wgrad", &gconv2d_wgrad, py::arg("dy"), py::arg("x"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"), py::arg("groups"), py::arg("out") = py::none(), py::arg("accumulate") = false);
   m.def("conv_bn_act_fwd", &conv_bn_act_fwd, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("gamma"),
         py::arg("beta"), py::arg("running_mean"), py::arg("running_var"), py::arg("num_batches_tracked"),
         py::arg("momentum"), py::arg("eps"), py::arg("training"), py::arg("stride"), py::arg("pad"), py::arg("pool"),
         py::arg("relu"), py::arg("residual"), py::arg("x_amax") = py::none(), py::arg("w_amax") = py::none(),
         py::arg("res_y") = py::none(), py::arg("res_stats") = py::none(), py::arg("defer_apply") = false,
-        py::arg("drop_scale") = py::none(),
+        py::arg("drop_scale") = py::none(), py::arg("groups") = 1,
         "fused conv + BN [+ residual] [+ ReLU] [+ 2x2 max-pool] forward; returns (out, y, stats, x_saved, out_amax, "
         "x_amax, w_amax, relu_mask). defer_apply: statistics only, out a shape-only placeholder; res_y / res_stats: "
         "the residual as such a deferred branch's raw output and stats, normalized inside this block's apply pass; "
@@ -74,6 +81,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("w_t") = py::none(), py::arg("part_in") = py::none(), py::arg("prev_y") = py::none(),
         py::arg("prev_stats") = py::none(), py::arg("prev_pool") = false, py::arg("prev_relu") = false,
         py::arg("prev_ps") = 2, py::arg("bias") = py::none(), py::arg("drop_scale") = py::none(),
+        py::arg("groups") = 1,
         "fused block backward; returns (dx, dw, db, dgamma, dbeta, dres, prev_part, dy_amax). prev_* describe the BN whose "
         "output is x: its statistics reduction is then fused into this block's data-gradient reduction and returned "
         "as prev_part (undefined when not fused), which that block's backward takes as part_in");

@@ -1320,6 +1320,144 @@ at::Tensor conv2d_wgrad_keep(const at::Tensor& dy, const at::Tensor& x, std::vec
   return wgrad_impl(dy, x, w_shape, stride, pad, out, accumulate, keep_c, dy_amax, x_amax, nullptr);
 }
 
+// ---------------------------------------------------------------- grouped 3x3 conv (gconv.hip)
+// The direct fp32 kernels' domain: 3x3, pad 1, stride 1 or 2, whole groups of 4k <= 64 channels on both
+// sides, 32-bit element indices. Everything else is the caller's to route elsewhere.
+namespace {
+struct GconvDims {
+  int N, C, H, W, Co, P, Q, G, cgi, cgo;
+  long long M;
+};
+GconvDims gconv_dims(const char* op, c10::IntArrayRef xs, c10::IntArrayRef ws, int64_t stride, int64_t pad,
+                     int64_t groups) {
+  TORCH_CHECK(xs.size() == 4 && ws.size() == 4, op, ": expects a 4-D input and weight");
+  TORCH_CHECK(ws[2] == 3 && ws[3] == 3 && pad == 1 && (stride == 1 || stride == 2), op,
+              ": the grouped kernels take 3x3 / pad 1 / stride 1 or 2, got ", ws[2], "x", ws[3], " pad ", pad,
+              " stride ", stride);
+  GconvDims d{};
+  d.N = xs[0]; d.C = xs[1]; d.H = xs[2]; d.W = xs[3]; d.Co = ws[0]; d.G = (int)groups; d.cgi = ws[1];
+  TORCH_CHECK(groups >= 1 && d.C % groups == 0 && d.Co % groups == 0 && d.C / groups == d.cgi, op, ": ", d.C,
+              " -> ", d.Co, " channels do not split into ", groups, " groups of ", d.cgi, " inputs");
+  d.cgo = d.Co / (int)groups;
+  TORCH_CHECK(d.cgi % 4 == 0 && d.cgo % 4 == 0 && d.cgi <= 64 && d.cgo <= 64, op,
+              ": channels per group must be multiples of 4 and <= 64, got ", d.cgi, " -> ", d.cgo);
+  d.P = (d.H + 2 - 3) / (int)stride + 1;
+  d.Q = (d.W + 2 - 3) / (int)stride + 1;
+  d.M = (long long)d.N * d.P * d.Q;
+  TORCH_CHECK(d.N > 0 && d.H > 0 && d.W > 0 && (long long)d.N * d.H * d.W * d.C < (1LL << 31) &&
+                  d.M * d.Co < (1LL << 31),
+              op, ": tensors must be non-empty and below 2^31 elements");
+  return d;
+}
+void check_align16(const at::Tensor& t, const char* op) {
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr<float>()) & 15) == 0, op, ": tensors must be 16-byte aligned");
+}
+}  // namespace
+
+// {y} or, with want_stats, {y, part [ceil(M / 64), Co, 2], rows per part}: conv2d_fwd's contract
+std::vector<at::Tensor> gconv2d_fwd(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias,
+                                    int64_t stride, int64_t pad, int64_t groups, bool want_stats) {
+  check_f32_cuda(x_, "x");
+  check_f32_cuda(w_, "weight");
+  const GconvDims d = gconv_dims("gconv2d_fwd", x_.sizes(), w_.sizes(), stride, pad, groups);
+  const at::Tensor x = nhwc(x_), w = nhwc(w_);
+  auto opts = x.options();
+  at::Tensor y = at::empty({d.N, d.Co, d.P, d.Q}, opts.memory_format(at::MemoryFormat::ChannelsLast));
+  at::Tensor part, bv;
+  GConvParams p{};
+  if (bias.has_value() && bias->defined()) {
+    check_f32_cuda(*bias, "bias");
+    TORCH_CHECK(bias->numel() == d.Co, "gconv2d_fwd: bias must hold one value per output channel");
+    bv = bias->contiguous();
+    check_align16(bv, "gconv2d_fwd");
+    p.bias = bv.data_ptr<float>();
+  }
+  if (want_stats) {
+    part = at::empty({(d.M + kGconvRows - 1) / kGconvRows, d.Co, 2}, opts);
+    p.part = part.data_ptr<float>();
+  }
+  check_align16(x, "gconv2d_fwd");
+  check_align16(w, "gconv2d_fwd");
+  p.src = x.data_ptr<float>();
+  p.w = w.data_ptr<float>();
+  p.dst = y.data_ptr<float>();
+  p.N = d.N; p.SH = d.H; p.SW = d.W; p.OH = d.P; p.OW = d.Q; p.G = d.G; p.cgi = d.cgi; p.cgo = d.cgo;
+  p.stride = (int)stride; p.M = (int)d.M;
+  gemm_log_add("gconv_fwd", d.M, d.Co, 9LL * d.cgi, kGconvRows, 64, 1);
+  gconv_fwd_launch(p, cur_stream());
+  if (want_stats) return {y, part, at::full({1}, kGconvRows, opts.dtype(at::kInt).device(at::kCPU))};
+  return {y};
+}
+
+// dX [N, C, H, W] (+ addend, accumulated into the addend in place as dgrad_impl does)
+at::Tensor gconv2d_dgrad(const at::Tensor& dy_, const at::Tensor& w_, std::vector<int64_t> in_shape, int64_t stride,
+                         int64_t pad, int64_t groups, const c10::optional<at::Tensor>& addend) {
+  check_f32_cuda(dy_, "grad_output");
+  check_f32_cuda(w_, "weight");
+  const GconvDims d = gconv_dims("gconv2d_dgrad", in_shape, w_.sizes(), stride, pad, groups);
+  TORCH_CHECK(dy_.dim() == 4 && dy_.size(0) == d.N && dy_.size(1) == d.Co && dy_.size(2) == d.P && dy_.size(3) == d.Q,
+              "gconv2d_dgrad: grad_output does not match the input shape");
+  const at::Tensor dy = nhwc(dy_), w = nhwc(w_);
+  auto opts = dy.options();
+  const bool has_add = addend.has_value() && addend->defined();
+  if (has_add)
+    TORCH_CHECK(addend->is_cuda() && addend->scalar_type() == at::kFloat &&
+                    addend->is_contiguous(at::MemoryFormat::ChannelsLast) && addend->sizes() == c10::IntArrayRef(in_shape),
+                "gconv2d_dgrad: the addend must be a channels_last fp32 tensor of the input's shape");
+  at::Tensor dx = has_add ? *addend : at::empty({d.N, d.C, d.H, d.W}, opts.memory_format(at::MemoryFormat::ChannelsLast));
+  check_align16(dy, "gconv2d_dgrad");
+  check_align16(w, "gconv2d_dgrad");
+  check_align16(dx, "gconv2d_dgrad");
+  GConvParams p{};
+  p.src = dy.data_ptr<float>();
+  p.w = w.data_ptr<float>();
+  p.dst = dx.data_ptr<float>();
+  p.addend = has_add ? dx.data_ptr<float>() : nullptr;
+  p.N = d.N; p.SH = d.P; p.SW = d.Q; p.OH = d.H; p.OW = d.W; p.G = d.G; p.cgi = d.cgi; p.cgo = d.cgo;
+  p.stride = (int)stride; p.M = d.N * d.H * d.W;
+  gemm_log_add("gconv_dgrad", p.M, d.C, 9LL * d.cgo, kGconvRows, 64, 1);
+  gconv_dgrad_launch(p, cur_stream());
+  return dx;
+}
+
+// dW (channels_last [Co, C / groups, 3, 3]); written into `out` when given (accumulating if asked)
+at::Tensor gconv2d_wgrad(const at::Tensor& dy_, const at::Tensor& x_, std::vector<int64_t> w_shape, int64_t stride,
+                         int64_t pad, int64_t groups, const c10::optional<at::Tensor>& out, bool accumulate) {
+  check_f32_cuda(dy_, "grad_output");
+  check_f32_cuda(x_, "input");
+  const GconvDims d = gconv_dims("gconv2d_wgrad", x_.sizes(), w_shape, stride, pad, groups);
+  TORCH_CHECK(dy_.dim() == 4 && dy_.size(0) == d.N && dy_.size(1) == d.Co && dy_.size(2) == d.P && dy_.size(3) == d.Q,
+              "gconv2d_wgrad: grad_output does not match the input and weight shapes");
+  const at::Tensor dy = nhwc(dy_), x = nhwc(x_);
+  auto opts = x.options();
+  const long long n = (long long)d.Co * 9 * d.cgi;
+  at::Tensor dw;
+  if (out.has_value() && out->defined()) {
+    dw = *out;
+    TORCH_CHECK(dw.is_cuda() && dw.scalar_type() == at::kFloat && dw.numel() == n &&
+                    (dw.is_contiguous(at::MemoryFormat::ChannelsLast) || dw.dim() == 1),
+                "gconv2d_wgrad: out must be the weight's channels_last fp32 slot");
+  } else {
+    dw = at::empty({d.Co, d.cgi, 3, 3}, opts.memory_format(at::MemoryFormat::ChannelsLast));
+    accumulate = false;
+  }
+  check_align16(dy, "gconv2d_wgrad");
+  check_align16(x, "gconv2d_wgrad");
+  hipStream_t st = cur_stream();
+  const GConvChunks ch = gconv_wgrad_chunks(d.M, d.G, d.cgi, d.cgo, num_cus());
+  at::Tensor slab = at::empty({ch.S, n}, opts);
+  GConvWgradParams p{};
+  p.dy = dy.data_ptr<float>();
+  p.x = x.data_ptr<float>();
+  p.slab = slab.data_ptr<float>();
+  p.N = d.N; p.H = d.H; p.W = d.W; p.P = d.P; p.Q = d.Q; p.G = d.G; p.cgi = d.cgi; p.cgo = d.cgo;
+  p.stride = (int)stride; p.M = (int)d.M; p.tiles_per_chunk = ch.tiles_per_chunk;
+  gemm_log_add("gconv_wgrad", d.Co, 9LL * d.cgi, d.M, 64, 64, ch.S);
+  gconv_wgrad_launch(p, ch.S, st);
+  slab_sum_launch(slab.data_ptr<float>(), ch.S, n, dw.data_ptr<float>(), accumulate, st);
+  return dw;
+}
+
 // ---------------------------------------------------------------- RGB stem (stem.hip)
 bool stem_enabled() { return true; }
 static bool bn_fin_enabled(bool bwd);
@@ -1423,8 +1561,12 @@ std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w
                                         const c10::optional<at::Tensor>& w_amax,
                                         const c10::optional<at::Tensor>& res_y,
                                         const c10::optional<at::Tensor>& res_stats, bool defer_apply,
-                                        const c10::optional<at::Tensor>& drop_scale) {
+                                        const c10::optional<at::Tensor>& drop_scale, int64_t groups) {
   const bool lazy_res = res_y.has_value() && res_y->defined();
+  // a grouped conv (gconv.hip) is a plain conv -> BN -> act: the models' grouped conv is nothing else
+  TORCH_CHECK(groups == 1 || (!(residual.has_value() && residual->defined()) && !lazy_res && !pool && !defer_apply &&
+                              !(drop_scale.has_value() && drop_scale->defined())),
+              "conv_bn_act_fwd: groups > 1 takes no residual, pool, defer_apply or drop_scale");
   // stochastic depth: one scale per image on the BatchNorm output of a residual block (drop_path.h)
   const float* dsp = drop_scale_ptr(drop_scale, x, "conv_bn_act_fwd");
   TORCH_CHECK(!dsp || (((residual.has_value() && residual->defined()) || lazy_res) && !pool && !defer_apply),
@@ -1432,24 +1574,27 @@ std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w
               "neither pool nor defer_apply");
   // RGB stem (3x3 / stride 1 / pad 1, Cin <= 4, training BN): one exact-fp32 MFMA kernel reading
   // the raw NHWC input, no channel padding, no operand scales (stem.hip)
-  if (stem_enabled() && stem_ok((int)x.size(1), (int)w.size(2), (int)w.size(3), stride, pad, (int)w.size(0)) &&
-      training && !(residual.has_value() && residual->defined()) && !lazy_res && !defer_apply)
+  if (groups == 1 && stem_enabled() &&
+      stem_ok((int)x.size(1), (int)w.size(2), (int)w.size(3), stride, pad, (int)w.size(0)) && training && !(residual.has_value() && residual->defined()) && !lazy_res && !defer_apply)
     return stem_bn_act_fwd(x, w, b, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, pool,
                            relu);
   // other stems: zero-pad 3 -> 4 channels so the float4 gather path runs (the padded input is what
   // backward needs, so it is returned for saving)
-  const bool padc = (x.size(1) % 4) != 0;
+  const bool padc = groups == 1 && (x.size(1) % 4) != 0;
   at::Tensor pad_amax;  // the padding pass measures x on the way (f16x2)
   const at::Tensor xin = padc ? pad_channels4(nhwc(x), f16x2_mode() ? &pad_amax : nullptr) : x;
   const at::Tensor win = padc ? pad_channels4(nhwc(w)) : w;
   // f16x2 operand maxima: x's from its producer when given; W's once per step, reused by backward
   // (zero channel padding does not change a maximum; a given x act max of the unpadded tensor is
   // not used for the padded one, whose channel count differs)
-  const at::Tensor xa = act_max(xin, pad_amax.defined() ? c10::optional<at::Tensor>(pad_amax)
-                                     : padc ? c10::optional<at::Tensor>() : x_amax,
-                                cur_stream());
-  const at::Tensor wa = weight_max(win, padc ? c10::optional<at::Tensor>() : w_amax);
-  std::vector<at::Tensor> r = conv2d_fwd(xin, win, b, stride, pad, training, xa, wa);
+  // (the grouped kernels are exact fp32: no operand maxima)
+  const at::Tensor xa = groups > 1 ? at::Tensor()
+                                   : act_max(xin, pad_amax.defined() ? c10::optional<at::Tensor>(pad_amax)
+                                                  : padc ? c10::optional<at::Tensor>() : x_amax,
+                                             cur_stream());
+  const at::Tensor wa = groups > 1 ? at::Tensor() : weight_max(win, padc ? c10::optional<at::Tensor>() : w_amax);
+  std::vector<at::Tensor> r = groups > 1 ? gconv2d_fwd(xin, win, b, stride, pad, groups, training)
+                                         : conv2d_fwd(xin, win, b, stride, pad, training, xa, wa);
   at::Tensor y = r[0];
   const int N = y.size(0), C = y.size(1), H = y.size(2), W = y.size(3);
   TORCH_CHECK(C % 4 == 0, "BatchNorm channel count must be a multiple of 4");
@@ -1552,8 +1697,12 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout_, const at::Tenso
                                         const c10::optional<at::Tensor>& prev_y,
                                         const c10::optional<at::Tensor>& prev_stats, bool prev_pool, bool prev_relu,
                                         int64_t prev_ps, const c10::optional<at::Tensor>& bias,
-                                        const c10::optional<at::Tensor>& drop_scale) {
+                                        const c10::optional<at::Tensor>& drop_scale, int64_t groups) {
   check_f32_cuda(gout_, "grad_output");
+  auto given = [](const c10::optional<at::Tensor>& o) { return o.has_value() && o->defined(); };
+  TORCH_CHECK(groups == 1 || (!given(zout_) && !pool && !given(dx_addend) && !given(part_in) && !given(prev_y) &&
+                              !given(drop_scale)),
+              "conv_bn_act_bwd: groups > 1 takes no residual, pool, dx_addend, BN hand-off or drop_scale");
   // stochastic depth (the forward's drop_scale): the gradient at the BN output is drop_scale[img] * dz;
   // the shortcut (dres) gets dz itself
   const float* dsp = drop_scale_ptr(drop_scale, y, "conv_bn_act_bwd");
@@ -1613,7 +1762,7 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout_, const at::Tenso
   // RGB stem without an input gradient (VGG layer 0): the weight-gradient kernel applies the
   // BN / ReLU / pool backward on the fly, so dy is never materialised (stem.hip)
   const int cin = (int)x.size(1);
-  const bool stem_path = stem_enabled() && !need_dx && training && pool && relu && !zout.defined() && fused_db &&
+  const bool stem_path = groups == 1 && stem_enabled() && !need_dx && training && pool && relu && !zout.defined() && fused_db &&
                          C == 64 && stem_ok(cin, (int)w.size(2), (int)w.size(3), stride, pad, C) &&
                          cin == (int)w.size(1) && (H % 2) == 0 && (W % 2) == 0;
   // few statistics partials (the deep layers): finalize and apply in one launch (bn_bwd_fin_apply_kernel),
@@ -1670,8 +1819,16 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout_, const at::Tenso
   const c10::optional<at::Tensor> dya = dy_amax.defined() ? c10::optional<at::Tensor>(dy_amax) : c10::nullopt;
   if (sep_db)
     chan_finalize_launch(dbpart.data_ptr<float>(), nblk, C, nullptr, db.data_ptr<float>(), nullptr, false, st);
-  // x may carry zero-padded channels (RGB stem, see conv_bn_act_fwd)
-  const bool padc = x.size(1) != w.size(1);
+  if (groups > 1) {  // the direct grouped kernels: nothing to pair, defer or hand on
+    at::Tensor gdw = gconv2d_wgrad(dy, x, {w.size(0), w.size(1), w.size(2), w.size(3)}, stride, pad, groups, dw_out,
+                                   false);
+    at::Tensor gdx;
+    if (need_dx)
+      gdx = gconv2d_dgrad(dy, w, {x.size(0), x.size(1), x.size(2), x.size(3)}, stride, pad, groups, c10::nullopt);
+    return {gdx, gdw, db, dgamma, dbeta, at::Tensor(), at::Tensor(), dy_amax};
+  }
+  // x may carry zero-padded channels (RGB stem, see conv_bn_act_fwd); a grouped conv's x.size(1) != w.size(1) too
+  const bool padc = groups == 1 && x.size(1) != w.size(1);
   // (running the weight gradient on a side stream beside the data gradient was measured 2x slower
   // on MI355X: two full-occupancy GEMM grids compete instead of overlapping; docs/PERF.md)
   at::Tensor dx, dw;

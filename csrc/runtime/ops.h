@@ -32,6 +32,14 @@ at::Tensor conv2d_wgrad_keep(const at::Tensor& dy, const at::Tensor& x, std::vec
                              int64_t pad, const c10::optional<at::Tensor>& out, bool accumulate, int64_t keep_c,
                              const c10::optional<at::Tensor>& dy_amax = c10::nullopt,
                              const c10::optional<at::Tensor>& x_amax = c10::nullopt);
+// Grouped 3x3 conv (pad 1, stride 1 or 2; channels per group multiples of 4, <= 64) by the direct fp32 kernels of
+// gconv.hip; w [Co, C / groups, 3, 3]. gconv2d_fwd returns conv2d_fwd's {y[, part, rows per part]}.
+std::vector<at::Tensor> gconv2d_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
+                                    int64_t stride, int64_t pad, int64_t groups, bool want_stats);
+at::Tensor gconv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, std::vector<int64_t> in_shape, int64_t stride,
+                         int64_t pad, int64_t groups, const c10::optional<at::Tensor>& addend);
+at::Tensor gconv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, std::vector<int64_t> w_shape, int64_t stride,
+                         int64_t pad, int64_t groups, const c10::optional<at::Tensor>& out, bool accumulate);
 std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b,
                                         const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta,
                                         const c10::optional<at::Tensor>& running_mean,
@@ -44,7 +52,8 @@ std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w
                                         const c10::optional<at::Tensor>& res_y = c10::nullopt,
                                         const c10::optional<at::Tensor>& res_stats = c10::nullopt,
                                         bool defer_apply = false,
-                                        const c10::optional<at::Tensor>& drop_scale = c10::nullopt);
+                                        const c10::optional<at::Tensor>& drop_scale = c10::nullopt,
+                                        int64_t groups = 1);
 at::Tensor act_max_of(const at::Tensor& t);
 int64_t act_max_memsets();
 int64_t act_max_copies();
@@ -68,7 +77,8 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout, const at::Tensor
                                         const c10::optional<at::Tensor>& prev_stats = c10::nullopt,
                                         bool prev_pool = false, bool prev_relu = false, int64_t prev_ps = 2,
                                         const c10::optional<at::Tensor>& bias = c10::nullopt,
-                                        const c10::optional<at::Tensor>& drop_scale = c10::nullopt);
+                                        const c10::optional<at::Tensor>& drop_scale = c10::nullopt,
+                                        int64_t groups = 1);
 at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b);
 std::vector<at::Tensor> linear_bwd(const at::Tensor& gy, const at::Tensor& x, const at::Tensor& w, bool need_dx,
                                    bool has_bias, const c10::optional<at::Tensor>& dw_out,

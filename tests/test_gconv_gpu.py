@@ -1,0 +1,183 @@
+"""Grouped 3x3 convolution on the GPU (csrc/kernels/gconv.hip): the three ops against float64
+`F.conv2d(..., groups=G)` under the project's fp32 dot-product bound, the fused conv -> BN -> ReLU block and
+`conv_gn_act` with a grouped conv, and one training step of a small ResNeXt against the float64 reference path.
+
+The ops are held to `_gemm_util.fp32_bound` (a sequential fp32 FMA chain of length K sits inside it by a factor
+of 4); the block and the step to 4 x what the same composition in float32 torch on the CPU misses float64 by,
+a block tensor plus 1e-6 of its scale (test_gn_gpu.py's criterion)."""
+import copy
+import functools
+import json
+import os
+import subprocess
+import sys
+import types
+
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from _gemm_util import check_bound, cl, fp32_bound, lib, make_data
+
+pytestmark = pytest.mark.gpu
+
+# (N, C, H, W, Co, G, stride)
+CASES = [
+    (2, 24, 7, 5, 24, 6, 1),     # Cg = 4, channel block not filled, odd map, row-tile tail
+    (2, 24, 7, 5, 24, 6, 2),     # stride 2 on an odd map (P, Q = 4, 3), parity predicate at the border
+    (3, 40, 9, 9, 40, 5, 2),     # Cg = 8, N P Q not a multiple of any tile
+    (2, 48, 6, 10, 48, 3, 1),    # Cg = 16
+    (2, 64, 5, 5, 64, 2, 2),     # Cg = 32
+    (1, 128, 4, 6, 128, 2, 1),   # Cg = 64, weights sliced through LDS
+    (2, 16, 8, 8, 32, 4, 1),     # Cg_in = 4 != Cg_out = 8
+    (2, 32, 1, 1, 32, 8, 1),     # a 1x1 map: eight of nine taps are padding
+]
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case, kind):
+    """fp32 CPU inputs and the float64 y, dx, dw of one grouped conv with the sum_i |a_i||b_i| of each element.
+    Computed once per (case, kind); read only."""
+    N, C, H, W, Co, G, s = case
+    gen = torch.Generator().manual_seed(11)
+    x = make_data(kind, (N, C, H, W), gen)
+    w = (torch.randn(Co, C // G, 3, 3, generator=gen) * (1.0 / (9 * C // G) ** 0.5)).float()
+    conv = lambda a, b: F.conv2d(a, b, None, s, 1, 1, G)
+    xd, wd = x.double().requires_grad_(), w.double().requires_grad_()
+    y = conv(xd, wd)
+    gy = make_data(kind, tuple(y.shape), gen)
+    y.backward(gy.double())
+    xa, wa = xd.detach().abs().requires_grad_(), wd.detach().abs().requires_grad_()
+    abs_y = conv(xa, wa)
+    abs_y.backward(gy.double().abs())
+    return types.SimpleNamespace(x=x, w=w, gy=gy, y=y.detach(), dx=xd.grad, dw=wd.grad, abs_y=abs_y.detach(),
+                                 abs_dx=xa.grad, abs_dw=wa.grad, K=(9 * C // G, 9 * Co // G, y.numel() // Co))
+
+
+def run_ops(case, kind, out=None, accumulate=False):
+    N, C, H, W, Co, G, s = case
+    r, L = reference(case, kind), lib()
+    x, w, gy = cl(r.x.cuda()), cl(r.w.cuda()), cl(r.gy.cuda())
+    y = L.gconv2d_fwd(x, w, None, s, 1, G, False)[0]
+    dx = L.gconv2d_dgrad(gy, w, [N, C, H, W], s, 1, G, None)
+    dw = L.gconv2d_wgrad(gy, x, list(w.shape), s, 1, G, out, accumulate)
+    return y, dx, dw
+
+
+@pytest.mark.parametrize("kind", ["gauss", "heavy"])
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c)))
+def test_ops_match_fp64(case, kind):
+    r = reference(case, kind)
+    y, dx, dw = run_ops(case, kind)
+    check_bound("y", y, r.y, r.abs_y, r.K[0])
+    check_bound("dx", dx, r.dx, r.abs_dx, r.K[1])
+    check_bound("dw", dw, r.dw, r.abs_dw, r.K[2])
+
+
+def test_wgrad_accumulates_and_calls_repeat_bitwise():
+    case, kind = CASES[2], "heavy"
+    r = reference(case, kind)
+    first, again = run_ops(case, kind), run_ops(case, kind)
+    for name, a, b in zip(("y", "dx", "dw"), first, again):
+        assert torch.equal(a, b), f"{name}: a second call differs bitwise"
+    base = make_data("gauss", tuple(r.w.shape), torch.Generator().manual_seed(3))
+    slot = cl(base.cuda())
+    dw = run_ops(case, kind, out=slot, accumulate=True)[2]
+    assert dw.data_ptr() == slot.data_ptr()
+    # the slot's own add rounds once more: 2^-24 |base + dw| <= 2^-24 (|base| + sum |a||b|), with a factor 2
+    check_bound("dw += ", dw, r.dw + base.double(), r.abs_dw, r.K[2], extra=2.0 ** -23 * (base.double().abs() + r.abs_dw))
+
+
+# ------------------------------------------------------------------------------ the fused block
+def block_tensors(case, norm, device, dtype):
+    """(out, dx, dW, dgamma, dbeta[, running mean, running var]) of conv -> norm -> ReLU in training mode."""
+    from cs744_distributed_data_parallel_amd.ops import functional as CF
+
+    N, C, H, W, Co, G, s = case
+    r = reference(case, "gauss")
+    conv = nn.Conv2d(C, Co, 3, s, 1, groups=G, bias=False)
+    nm = nn.BatchNorm2d(Co) if norm == "bn" else nn.GroupNorm(Co // 8, Co)
+    with torch.no_grad():
+        conv.weight.copy_(r.w)
+        gen = torch.Generator().manual_seed(5)
+        nm.weight.copy_(1.0 + 0.5 * torch.randn(Co, generator=gen))
+        nm.bias.copy_(torch.randn(Co, generator=gen))
+    conv, nm = conv.to(device=device, dtype=dtype), nm.to(device=device, dtype=dtype)
+    x = r.x.to(device=device, dtype=dtype, copy=True)  # (a copy: the reference stays as it is)
+    if device == "cuda":
+        conv.weight.data = cl(conv.weight.data)
+        x = cl(x)
+    x.requires_grad_()
+    fn = CF.conv_bn_act if norm == "bn" else CF.conv_gn_act
+    out = fn(x, conv, nm, relu=True)
+    out.backward(r.gy.to(device=device, dtype=dtype))
+    ts = [out, x.grad, conv.weight.grad, nm.weight.grad, nm.bias.grad]
+    ts += [nm.running_mean, nm.running_var] if norm == "bn" else []
+    return [t.detach().double().cpu().reshape(-1) for t in ts]
+
+
+@pytest.mark.parametrize("case,norm", [(CASES[1], "bn"), (CASES[3], "bn"), (CASES[2], "gn")],
+                         ids=["bn_cg4_s2", "bn_cg16", "gn_cg8_s2"])
+def test_block_matches_fp64(case, norm):
+    ref = block_tensors(case, norm, "cpu", torch.float64)
+    f32 = block_tensors(case, norm, "cpu", torch.float32)
+    got = block_tensors(case, norm, "cuda", torch.float32)
+    bad = []
+    for name, a, b, c in zip(("out", "dx", "dW", "dgamma", "dbeta", "running_mean", "running_var"), got, ref, f32):
+        err, yard, scale = (a - b).abs().max().item(), (c - b).abs().max().item(), b.abs().max().item()
+        print(f"gconv block {norm} {name}: kernel err {err:.3e}  fp32 torch err {yard:.3e}")
+        if not err <= 4.0 * yard + 1e-6 * scale:
+            bad.append((name, err, yard))
+    assert not bad, bad
+
+
+def log_child():
+    """Runs in a fresh process under CDP_GEMM_LOG=1 (the flag is read once per process)."""
+    block_tensors(CASES[1], "bn", "cuda", torch.float32)
+    block_tensors(CASES[2], "gn", "cuda", torch.float32)
+    print("GCONV_LOG " + json.dumps([t[0] for t in lib().gemm_log(True)]))
+
+
+def test_block_launches_only_the_grouped_kernels():
+    tests = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, CDP_GEMM_LOG="1")
+    env["PYTHONPATH"] = os.pathsep.join([os.path.dirname(tests), tests, env.get("PYTHONPATH", "")])
+    r = subprocess.run([sys.executable, "-c", "import test_gconv_gpu as t; t.log_child()"], env=env,
+                       capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("GCONV_LOG ")]
+    assert len(line) == 1, r.stdout[-2000:]
+    assert json.loads(line[0][len("GCONV_LOG "):]) == ["gconv_fwd", "gconv_wgrad", "gconv_dgrad"] * 2
+
+
+# ------------------------------------------------------------------------------ one training step
+def step(ref, x, y, device, dtype):
+    net = copy.deepcopy(ref).to(device=device, dtype=dtype)
+    xin = x.to(device=device, dtype=dtype)
+    if device == "cuda":
+        xin = cl(xin)
+    loss = F.cross_entropy(net(xin), y.to(device))
+    loss.backward()
+    return loss.item(), [p.grad.double().cpu() for p in net.parameters()]
+
+
+def step_error(got, want):
+    worst = abs(got[0] - want[0]) / abs(want[0])
+    return max([worst] + [((g - g64).norm() / g64.norm()).item() for g, g64 in zip(got[1], want[1])])
+
+
+def test_resnext_step_matches_reference():
+    """Grouped convs of Cg = 4, 8, 16, 32, two of them stride 2; max(relative loss error, worst parameter
+    gradient's |g - g64|_2 / |g64|_2) held to 4 x the float32 CPU reference path's."""
+    from cs744_distributed_data_parallel_amd.models.resnet import Bottleneck, ResNet
+
+    torch.manual_seed(7)
+    ref = ResNet(Bottleneck, [1, 1, 1, 1], groups=8, width_per_group=4, num_classes=10)
+    assert [ref.get_submodule(f"layer{i}.0.conv2").in_channels // 8 for i in (1, 2, 3, 4)] == [4, 8, 16, 32]
+    x, y = torch.randn(2, 3, 32, 32), torch.tensor([3, 8])
+    want = step(ref, x, y, "cpu", torch.float64)
+    yard = step_error(step(ref, x, y, "cpu", torch.float32), want)
+    err = step_error(step(ref, x, y, "cuda", torch.float32), want)
+    print(f"gconv step: native {err:.3e}  fp32 cpu {yard:.3e}  ratio {err / yard:.2f}")
+    assert err <= 4.0 * yard
