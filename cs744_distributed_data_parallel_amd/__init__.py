@@ -20,7 +20,8 @@ from .data import MixTarget
 from .models import (VGG11, VGG13, VGG16, VGG19, ResNet, get_model, resnet18, resnet34, resnet50, resnet101, resnet152,
                      resnet18_gn, resnet34_gn, resnet50_gn, resnet101_gn, resnet152_gn, seresnet18, seresnet34,
                      seresnet50, seresnet101, seresnet152, resnext50_32x4d, resnext101_32x8d, resnext101_64x4d,
-                     seresnext50_32x4d, wide_resnet50_2, wide_resnet101_2)
+                     seresnext50_32x4d, wide_resnet50_2, wide_resnet101_2, MobileNetV1, mobilenet_v1,
+                     mobilenet_v1_075, mobilenet_v1_050, mobilenet_v1_025)
 from .ops import BinaryCrossEntropy, CrossEntropyLoss
 from .optim import LAMB, LARS, SGD, AdamW, LRSchedule, clip_grad_norm_
 from .parallel import DDP, DistributedDataParallel
@@ -30,7 +31,7 @@ __version__ = "0.1.0"
 __all__ = [
     "_native", "data", "distributed", "models", "ops", "optim", "parallel", "utils",
     "VGG11", "VGG13", "VGG16", "VGG19", "get_model", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
-    "resnet152", "resnet18_gn", "resnet34_gn", "resnet50_gn", "resnet101_gn", "resnet152_gn", "seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152", "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "seresnext50_32x4d", "wide_resnet50_2", "wide_resnet101_2", "CrossEntropyLoss", "BinaryCrossEntropy", "MixTarget", "SGD", "LARS", "AdamW", "LAMB", "LRSchedule", "clip_grad_norm_",
+    "resnet152", "resnet18_gn", "resnet34_gn", "resnet50_gn", "resnet101_gn", "resnet152_gn", "seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152", "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "seresnext50_32x4d", "wide_resnet50_2", "wide_resnet101_2", "MobileNetV1", "mobilenet_v1", "mobilenet_v1_075", "mobilenet_v1_050", "mobilenet_v1_025", "CrossEntropyLoss", "BinaryCrossEntropy", "MixTarget", "SGD", "LARS", "AdamW", "LAMB", "LRSchedule", "clip_grad_norm_",
     "DDP", "DistributedDataParallel", "native_available",
 ]
 

@@ -1,4 +1,5 @@
-"""Model zoo: the reference's VGG family (CIFAR-shaped) and the ResNet family (ImageNet-shaped)."""
+"""Model zoo: the reference's VGG family (CIFAR-shaped) and the ResNet and MobileNetV1 families (ImageNet-shaped)."""
+from .mobilenet import MobileNetV1, mobilenet_v1, mobilenet_v1_025, mobilenet_v1_050, mobilenet_v1_075
 from .resnet import (ResNet, SEModule, resnet18, resnet18_gn, resnet34, resnet34_gn, resnet50, resnet50_gn, resnet101,
                      resnet101_gn, resnet152, resnet152_gn, seresnet18, seresnet34, seresnet50, seresnet101,
                      seresnet152, resnext50_32x4d, resnext101_32x8d, resnext101_64x4d, seresnext50_32x4d,
@@ -38,6 +39,14 @@ _REGISTRY.update({
     "wideresnet502": wide_resnet50_2,
     "wideresnet1012": wide_resnet101_2,
 })
+# depthwise-separable: MobileNetV1 at width multipliers 1, 0.75, 0.5 and 0.25 ("mobilenet_v1_050" and
+# "mobilenetv1_050" are one key: get_model strips "_" and "-")
+_REGISTRY.update({
+    "mobilenetv1": mobilenet_v1,
+    "mobilenetv1075": mobilenet_v1_075,
+    "mobilenetv1050": mobilenet_v1_050,
+    "mobilenetv1025": mobilenet_v1_025,
+})
 
 # input shape (C, H, W) and number of classes per family
 INPUT_SHAPES = {k: ((3, 32, 32), 10) if k.startswith("vgg") else ((3, 224, 224), 1000) for k in _REGISTRY}
@@ -61,5 +70,6 @@ __all__ = [
     "SEModule", "seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152",
     "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "seresnext50_32x4d", "wide_resnet50_2",
     "wide_resnet101_2",
+    "MobileNetV1", "mobilenet_v1", "mobilenet_v1_075", "mobilenet_v1_050", "mobilenet_v1_025",
     "get_model", "list_models", "INPUT_SHAPES",
 ]

@@ -302,7 +302,9 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
     pass; the BatchNorm statistics and the residual are untouched. It gets no gradient.
     A grouped ``conv`` (``conv.groups > 1``: 3x3, pad 1, stride 1 or 2, channels per group multiples of 4 and
     ``<= 64``) runs the direct fp32 kernels of csrc/kernels/gconv.hip inside the same block; it takes none of the
-    options above but ``relu`` (``ValueError`` otherwise).
+    options above but ``relu`` (``ValueError`` otherwise). So does a depthwise ``conv`` (``groups == C``, channel
+    multiplier 1, 3x3, pad 1, stride 1 or 2, ``C % 4 == 0``) on the kernels of csrc/kernels/dwconv.hip; any other
+    depthwise conv (5x5, dilated, a channel multiplier above 1, ``C % 4 != 0``) is a ``ValueError`` here.
     """
     if drop_scale is not None and (residual is None or pool or defer_apply):
         raise ValueError("conv_bn_act: drop_scale scales the branch of a residual block: it needs a residual and "
@@ -311,14 +313,16 @@ def conv_bn_act(x, conv, bn, relu: bool = True, pool: bool = False, residual=Non
     pad = conv.padding[0]
     groups = int(conv.groups)
     if groups > 1 and use_native(x):
-        # the direct grouped kernels (csrc/kernels/gconv.hip) serve a plain conv -> BN -> act
+        # the direct grouped (csrc/kernels/gconv.hip) and depthwise (dwconv.hip) kernels serve a plain
+        # conv -> BN -> act
         if (residual is not None or pool or defer_apply or drop_scale is not None or res_sink is not None
                 or dx_sink is not None or bn_link):
             raise ValueError("conv_bn_act: a grouped conv takes no residual, pool, defer_apply, drop_scale, "
                              "res_sink / dx_sink or bn_link")
-        if not _gconv_native(x, conv):
+        if not (_gconv_native(x, conv) or _dwconv_native(x, conv)):
             raise ValueError("conv_bn_act: a grouped conv must be 3x3 / pad 1 / stride 1 or 2 / dilation 1 with "
-                             f"channels per group multiples of 4 and <= 64. Got: {conv}")
+                             "channels per group multiples of 4 and <= 64, or depthwise (groups == C, channel "
+                             f"multiplier 1) with C a multiple of 4. Got: {conv}")
         w_amax = w_t = None  # a grouped weight's products are never a dense GEMM's operands
     if use_native(x):
         training = bn.training or not bn.track_running_stats
@@ -480,6 +484,33 @@ class _GConv2d(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+class _DWConv2d(torch.autograd.Function):
+    """A depthwise 3x3 conv over the three direct fp32 kernels (csrc/kernels/dwconv.hip); no operand scales."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride):
+        y = _native.lib().dwconv2d_fwd(x, w, b, stride, 1, False)[0]
+        ctx.stride = stride
+        ctx.params = (w, b)
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, w = ctx.saved_tensors
+        wp, bp = ctx.params
+        nig = ctx.needs_input_grad
+        C = _native.lib()
+        dw = dx = db = None
+        if nig[1]:
+            dw = C.dwconv2d_wgrad(gout, x, list(w.shape), ctx.stride, 1, _slot(wp, True), False)
+        if nig[0]:
+            dx = C.dwconv2d_dgrad(gout, w, list(x.shape), ctx.stride, 1, None)
+        if bp is not None and nig[2]:
+            db = gout.sum((0, 2, 3))
+        return dx, dw, db, None
+
+
 def _int_pair(v) -> bool:
     return isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, int) for e in v) and v[0] == v[1]
 
@@ -499,14 +530,26 @@ def _gconv_native(x, conv) -> bool:
     return x.numel() < 2 ** 31 and out < 2 ** 31
 
 
+def _dwconv_native(x, conv) -> bool:
+    """The depthwise kernels' domain: ``groups == in_channels == out_channels`` (channel multiplier 1), 3x3 / pad 1 /
+    stride 1 or 2 / dilation 1, ``C % 4 == 0``, float32 NCHW-shaped tensors below 2^31 elements."""
+    C = conv.in_channels
+    return (conv.groups == C and conv.out_channels == C and C > 1 and C % 4 == 0 and x.dim() == 4
+            and x.dtype == torch.float32 and x.shape[1] == C and tuple(conv.kernel_size) == (3, 3)
+            and tuple(conv.dilation) == (1, 1) and tuple(conv.stride) in ((1, 1), (2, 2))
+            and tuple(conv.padding) == (1, 1) and conv.padding_mode == "zeros" and 0 < x.numel() < 2 ** 31)
+
+
 def conv2d(x, conv):
     """``conv(x)`` for an ``nn.Conv2d``: the implicit-GEMM forward, data-gradient and weight-gradient kernels
     behind one autograd function, with the f16x2 operand scales taken from ``x``'s and the incoming gradient's
     producers and from the module's ``_cdp_wamax`` / ``_cdp_wt`` (:func:`weight_prep`) when they are there;
     ``dW`` goes straight into its arena slot. A grouped 3x3 conv (pad 1, stride 1 or 2, channels per group
-    multiples of 4 and <= 64) runs the direct fp32 kernels of csrc/kernels/gconv.hip the same way. Other grouped
-    convs (depthwise, 1x1, ...), dilated or non-square-stride convs and CPU tensors run ``F.conv2d`` (a bias
-    gradient is a torch reduction: the models' convs have none)."""
+    multiples of 4 and <= 64) runs the direct fp32 kernels of csrc/kernels/gconv.hip the same way, and a depthwise
+    3x3 conv (``groups == C``, channel multiplier 1, pad 1, stride 1 or 2, ``C % 4 == 0``) those of
+    csrc/kernels/dwconv.hip. Other grouped convs (1x1, 5x5 or dilated depthwise, a channel multiplier above 1,
+    ...), dilated or non-square-stride convs and CPU tensors run ``F.conv2d`` (a bias gradient is a torch
+    reduction: the models' convs have none)."""
     plain = (conv.groups == 1 and tuple(conv.dilation) == (1, 1) and _int_pair(conv.stride)
              and _int_pair(conv.padding) and conv.padding_mode == "zeros")
     if use_native(x) and plain and x.dim() == 4 and x.dtype == torch.float32:
@@ -514,6 +557,8 @@ def conv2d(x, conv):
                              getattr(conv, "_cdp_wamax", None), getattr(conv, "_cdp_wt", None))
     if use_native(x) and _gconv_native(x, conv):
         return _GConv2d.apply(x, conv.weight, conv.bias, conv.stride[0], conv.groups)
+    if use_native(x) and _dwconv_native(x, conv):
+        return _DWConv2d.apply(x, conv.weight, conv.bias, conv.stride[0])
     return conv(x)
 
 

@@ -196,10 +196,15 @@ def _is_resnet(name: str) -> bool:
         ("resnet", "seresnet", "resnext", "seresnext", "wideresnet"))
 
 
+def _is_mobilenet(name: str) -> bool:
+    """The MobileNetV1 models: ImageNet-shaped like the ResNets, but with none of their model flags."""
+    return name.lower().replace("-", "").replace("_", "").startswith("mobilenet")
+
+
 def build_data(args, device, train: bool):
     if args.data.startswith("cifar10-bin:"):
         return cifar10_binary(args.data.split(":", 1)[1], train=train, device=device)
-    if _is_resnet(args.model):
+    if _is_resnet(args.model) or _is_mobilenet(args.model):
         n = args.synthetic_size or (1281 if train else 500)
         return synthetic_imagenet(n, seed=0 if train else 1, device=device, size=args.stored_size)
     n = args.synthetic_size or (50000 if train else 10000)
@@ -483,7 +488,7 @@ def parse_args(argv=None):
     p.add_argument("--center-crop", type=float, default=None, metavar="FRAC",
                    help="test loader: the central FRAC of each side, resized to --crop-size")
     p.add_argument("--stored-size", type=int, default=224, metavar="S",
-                   help="side of the synthetic ImageNet-shaped images (resnet models)")
+                   help="side of the synthetic ImageNet-shaped images (resnet and mobilenet models)")
     p.add_argument("--eval-topk", type=int, default=None, metavar="K",
                    help="also report the top-K accuracy of the test set (stderr; ties go to the lower class index)")
     p.add_argument("--bucket-cap-mb", type=float, default=None)

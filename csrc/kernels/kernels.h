@@ -391,6 +391,30 @@ struct GConvChunks {
 GConvChunks gconv_wgrad_chunks(long long M, int G, int cgi, int cgo, int cus);
 void gconv_wgrad_launch(const GConvWgradParams& p, int S, hipStream_t st);
 
+// dwconv.hip: direct depthwise 3x3 convolution (groups == C == Co, pad 1, stride 1 or 2) in fp32 FMA; C a
+// multiple of 4; every index of src and dst below 2^31.
+int dwconv_rows(int C);  // rows of a workgroup's tile = rows per BatchNorm partial (64, or 128 below 64 channels)
+struct DwConvParams {
+  const float* src;     // forward: x NHWC [N][SH][SW][C]; data gradient: dY [N][SH][SW][C]
+  const float* w;       // [C][9]
+  float* dst;           // rows (n, oh, ow): forward y [M][C]; data gradient dX [M][C]
+  const float* bias;    // [C] or nullptr (forward)
+  const float* addend;  // optional: dst += addend (dst's layout; may alias dst)
+  float* part;          // forward: BN partials [ceil(M / dwconv_rows(C))][C][2] (mean, M2) or nullptr
+  int N, SH, SW, OH, OW, C, stride, M;
+  int flip;             // set by the launchers: tap 8 - k in place of tap k (the stride-1 data gradient)
+};
+void dwconv_fwd_launch(const DwConvParams& p, hipStream_t st);
+void dwconv_dgrad_launch(const DwConvParams& p, hipStream_t st);
+struct DwConvWgradParams {
+  const float* dy;  // [M][C], rows (n, p, q)
+  const float* x;   // NHWC [N][H][W][C]
+  float* slab;      // [S][C][9]
+  int N, H, W, P, Q, C, stride, M, tiles_per_chunk;
+};
+GConvChunks dwconv_wgrad_chunks(long long M, int C, int cus);
+void dwconv_wgrad_launch(const DwConvWgradParams& p, int S, hipStream_t st);
+
 // misc.hip
 // eps: label smoothing in [0, 1] (target distribution (1 - eps) onehot + eps / C; 0: the plain kernels'
 // arithmetic); topk >= 1: a row counts as correct when fewer than topk logits rank above its target's

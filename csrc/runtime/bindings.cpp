@@ -58,6 +58,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("pad"), py::arg("groups"), py::arg("addend") = py::none());
   m.def("gconv2d_wgrad", &gconv2d_wgrad, py::arg("dy"), py::arg("x"), py::arg("w_shape"), py::arg("stride"),
         py::arg("pad"), py::arg("groups"), py::arg("out") = py::none(), py::arg("accumulate") = false);
+  m.def("dwconv2d_fwd", &dwconv2d_fwd, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("stride"), py::arg("pad"),
+        py::arg("want_stats") = false,
+        "depthwise 3x3 conv forward by the direct fp32 kernels; (y[, BN partials, rows per partial])");
+  m.def("dwconv2d_dgrad", &dwconv2d_dgrad, py::arg("dy"), py::arg("w"), py::arg("in_shape"), py::arg("stride"),
+        py::arg("pad"), py::arg("addend") = py::none());
+  m.def("dwconv2d_wgrad", &dwconv2d_wgrad, py::arg("dy"), py::arg("x"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"), py::arg("out") = py::none(), py::arg("accumulate") = false);
   m.def("conv_bn_act_fwd", &conv_bn_act_fwd, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("gamma"),
         py::arg("beta"), py::arg("running_mean"), py::arg("running_var"), py::arg("num_batches_tracked"),
         py::arg("momentum"), py::arg("eps"), py::arg("training"), py::arg("stride"), py::arg("pad"), py::arg("pool"),

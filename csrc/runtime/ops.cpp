@@ -1458,6 +1458,145 @@ at::Tensor gconv2d_wgrad(const at::Tensor& dy_, const at::Tensor& x_, std::vecto
   return dw;
 }
 
+// ---------------------------------------------------------------- depthwise 3x3 conv (dwconv.hip)
+// The direct fp32 kernels' domain: groups == C == Co (w [C, 1, 3, 3]), pad 1, stride 1 or 2, C % 4 == 0, 32-bit
+// element indices. Everything else is the caller's to route elsewhere.
+namespace {
+struct DwDims {
+  int N, C, H, W, P, Q;
+  long long M;
+};
+DwDims dw_dims(const char* op, c10::IntArrayRef xs, c10::IntArrayRef ws, int64_t stride, int64_t pad) {
+  TORCH_CHECK(xs.size() == 4 && ws.size() == 4, op, ": expects a 4-D input and weight");
+  TORCH_CHECK(ws[2] == 3 && ws[3] == 3 && pad == 1 && (stride == 1 || stride == 2), op,
+              ": the depthwise kernels take 3x3 / pad 1 / stride 1 or 2, got ", ws[2], "x", ws[3], " pad ", pad,
+              " stride ", stride);
+  DwDims d{};
+  d.N = xs[0]; d.C = xs[1]; d.H = xs[2]; d.W = xs[3];
+  TORCH_CHECK(ws[0] == d.C && ws[1] == 1, op, ": the weight must be [C, 1, 3, 3] with C = ", d.C, " (groups == C, ",
+              "channel multiplier 1), got [", ws[0], ", ", ws[1], ", 3, 3]");
+  TORCH_CHECK(d.C % 4 == 0, op, ": the channel count must be a multiple of 4, got ", d.C);
+  d.P = (d.H + 2 - 3) / (int)stride + 1;
+  d.Q = (d.W + 2 - 3) / (int)stride + 1;
+  d.M = (long long)d.N * d.P * d.Q;
+  TORCH_CHECK(d.N > 0 && d.C > 0 && d.H > 0 && d.W > 0 && (long long)d.N * d.H * d.W * d.C < (1LL << 31), op,
+              ": tensors must be non-empty and below 2^31 elements");
+  return d;
+}
+// [C, 1, 3, 3] is [C][9] in memory whether contiguous or channels_last (the size-1 axis has no stride of its own)
+at::Tensor dw_weight(const at::Tensor& w) { return w.is_contiguous() ? w : w.contiguous(); }
+}  // namespace
+
+// {y} or, with want_stats, {y, part [ceil(M / rpp), C, 2], rows per part}: conv2d_fwd's contract
+std::vector<at::Tensor> dwconv2d_fwd(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias,
+                                     int64_t stride, int64_t pad, bool want_stats) {
+  check_f32_cuda(x_, "x");
+  check_f32_cuda(w_, "weight");
+  const DwDims d = dw_dims("dwconv2d_fwd", x_.sizes(), w_.sizes(), stride, pad);
+  const at::Tensor x = nhwc(x_), w = dw_weight(w_);
+  auto opts = x.options();
+  at::Tensor y = at::empty({d.N, d.C, d.P, d.Q}, opts.memory_format(at::MemoryFormat::ChannelsLast));
+  at::Tensor part, bv;
+  DwConvParams p{};
+  if (bias.has_value() && bias->defined()) {
+    check_f32_cuda(*bias, "bias");
+    TORCH_CHECK(bias->numel() == d.C, "dwconv2d_fwd: bias must hold one value per channel");
+    bv = bias->contiguous();
+    check_align16(bv, "dwconv2d_fwd");
+    p.bias = bv.data_ptr<float>();
+  }
+  const int rpp = dwconv_rows(d.C);
+  if (want_stats) {
+    part = at::empty({(d.M + rpp - 1) / rpp, d.C, 2}, opts);
+    p.part = part.data_ptr<float>();
+  }
+  check_align16(x, "dwconv2d_fwd");
+  check_align16(w, "dwconv2d_fwd");
+  p.src = x.data_ptr<float>();
+  p.w = w.data_ptr<float>();
+  p.dst = y.data_ptr<float>();
+  p.N = d.N; p.SH = d.H; p.SW = d.W; p.OH = d.P; p.OW = d.Q; p.C = d.C;
+  p.stride = (int)stride; p.M = (int)d.M;
+  gemm_log_add("dwconv_fwd", d.M, d.C, 9, rpp, d.C >= 64 ? 64 : 32, 1);
+  dwconv_fwd_launch(p, cur_stream());
+  if (want_stats) return {y, part, at::full({1}, rpp, opts.dtype(at::kInt).device(at::kCPU))};
+  return {y};
+}
+
+// dX [N, C, H, W] (+ addend, accumulated into the addend in place as dgrad_impl does)
+at::Tensor dwconv2d_dgrad(const at::Tensor& dy_, const at::Tensor& w_, std::vector<int64_t> in_shape, int64_t stride,
+                          int64_t pad, const c10::optional<at::Tensor>& addend) {
+  check_f32_cuda(dy_, "grad_output");
+  check_f32_cuda(w_, "weight");
+  const DwDims d = dw_dims("dwconv2d_dgrad", in_shape, w_.sizes(), stride, pad);
+  TORCH_CHECK(dy_.dim() == 4 && dy_.size(0) == d.N && dy_.size(1) == d.C && dy_.size(2) == d.P && dy_.size(3) == d.Q,
+              "dwconv2d_dgrad: grad_output does not match the input shape");
+  const at::Tensor dy = nhwc(dy_), w = dw_weight(w_);
+  auto opts = dy.options();
+  const bool has_add = addend.has_value() && addend->defined();
+  if (has_add)
+    TORCH_CHECK(addend->is_cuda() && addend->scalar_type() == at::kFloat &&
+                    addend->is_contiguous(at::MemoryFormat::ChannelsLast) && addend->sizes() == c10::IntArrayRef(in_shape),
+                "dwconv2d_dgrad: the addend must be a channels_last fp32 tensor of the input's shape");
+  at::Tensor dx = has_add ? *addend : at::empty({d.N, d.C, d.H, d.W}, opts.memory_format(at::MemoryFormat::ChannelsLast));
+  check_align16(dy, "dwconv2d_dgrad");
+  check_align16(w, "dwconv2d_dgrad");
+  check_align16(dx, "dwconv2d_dgrad");
+  DwConvParams p{};
+  p.src = dy.data_ptr<float>();
+  p.w = w.data_ptr<float>();
+  p.dst = dx.data_ptr<float>();
+  p.addend = has_add ? dx.data_ptr<float>() : nullptr;
+  p.N = d.N; p.SH = d.P; p.SW = d.Q; p.OH = d.H; p.OW = d.W; p.C = d.C;
+  p.stride = (int)stride; p.M = d.N * d.H * d.W;
+  gemm_log_add("dwconv_dgrad", p.M, d.C, stride == 1 ? 9 : 4, dwconv_rows(d.C), d.C >= 64 ? 64 : 32, 1);
+  dwconv_dgrad_launch(p, cur_stream());
+  return dx;
+}
+
+// dW [C, 1, 3, 3]; written into `out` when given (accumulating if asked)
+at::Tensor dwconv2d_wgrad(const at::Tensor& dy_, const at::Tensor& x_, std::vector<int64_t> w_shape, int64_t stride,
+                          int64_t pad, const c10::optional<at::Tensor>& out, bool accumulate) {
+  check_f32_cuda(dy_, "grad_output");
+  check_f32_cuda(x_, "input");
+  const DwDims d = dw_dims("dwconv2d_wgrad", x_.sizes(), w_shape, stride, pad);
+  TORCH_CHECK(dy_.dim() == 4 && dy_.size(0) == d.N && dy_.size(1) == d.C && dy_.size(2) == d.P && dy_.size(3) == d.Q,
+              "dwconv2d_wgrad: grad_output does not match the input and weight shapes");
+  const at::Tensor dy = nhwc(dy_), x = nhwc(x_);
+  auto opts = x.options();
+  const long long n = (long long)d.C * 9;
+  at::Tensor dw;
+  if (out.has_value() && out->defined()) {
+    dw = *out;
+    TORCH_CHECK(dw.is_cuda() && dw.scalar_type() == at::kFloat && dw.numel() == n &&
+                    (dw.is_contiguous() || dw.is_contiguous(at::MemoryFormat::ChannelsLast)),
+                "dwconv2d_wgrad: out must be the weight's dense fp32 slot");
+  } else {
+    dw = at::empty({d.C, 1, 3, 3}, opts);
+    accumulate = false;
+  }
+  check_align16(dy, "dwconv2d_wgrad");
+  check_align16(x, "dwconv2d_wgrad");
+  hipStream_t st = cur_stream();
+  const GConvChunks ch = dwconv_wgrad_chunks(d.M, d.C, num_cus());
+  at::Tensor slab = at::empty({ch.S, n}, opts);
+  DwConvWgradParams p{};
+  p.dy = dy.data_ptr<float>();
+  p.x = x.data_ptr<float>();
+  p.slab = slab.data_ptr<float>();
+  p.N = d.N; p.H = d.H; p.W = d.W; p.P = d.P; p.Q = d.Q; p.C = d.C;
+  p.stride = (int)stride; p.M = (int)d.M; p.tiles_per_chunk = ch.tiles_per_chunk;
+  gemm_log_add("dwconv_wgrad", d.C, 9, d.M, dwconv_rows(d.C), d.C >= 64 ? 64 : 32, ch.S);
+  dwconv_wgrad_launch(p, ch.S, st);
+  slab_sum_launch(slab.data_ptr<float>(), ch.S, n, dw.data_ptr<float>(), accumulate, st);
+  return dw;
+}
+
+// groups == C == Co with one filter per channel: the depthwise kernels' case of a grouped conv
+static bool is_depthwise(const at::Tensor& x, const at::Tensor& w, int64_t groups) {
+  return groups > 1 && x.dim() == 4 && w.dim() == 4 && groups == x.size(1) && w.size(0) == groups && w.size(1) == 1;
+}
+
 // ---------------------------------------------------------------- RGB stem (stem.hip)
 bool stem_enabled() { return true; }
 static bool bn_fin_enabled(bool bwd);
@@ -1593,8 +1732,10 @@ std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w
                                                   : padc ? c10::optional<at::Tensor>() : x_amax,
                                              cur_stream());
   const at::Tensor wa = groups > 1 ? at::Tensor() : weight_max(win, padc ? c10::optional<at::Tensor>() : w_amax);
-  std::vector<at::Tensor> r = groups > 1 ? gconv2d_fwd(xin, win, b, stride, pad, groups, training)
-                                         : conv2d_fwd(xin, win, b, stride, pad, training, xa, wa);
+  // (groups == C with one filter per channel: the depthwise kernels, dwconv.hip)
+  std::vector<at::Tensor> r = is_depthwise(xin, win, groups) ? dwconv2d_fwd(xin, win, b, stride, pad, training)
+                              : groups > 1                   ? gconv2d_fwd(xin, win, b, stride, pad, groups, training)
+                                                             : conv2d_fwd(xin, win, b, stride, pad, training, xa, wa);
   at::Tensor y = r[0];
   const int N = y.size(0), C = y.size(1), H = y.size(2), W = y.size(3);
   TORCH_CHECK(C % 4 == 0, "BatchNorm channel count must be a multiple of 4");
@@ -1820,11 +1961,15 @@ std::vector<at::Tensor> conv_bn_act_bwd(const at::Tensor& gout_, const at::Tenso
   if (sep_db)
     chan_finalize_launch(dbpart.data_ptr<float>(), nblk, C, nullptr, db.data_ptr<float>(), nullptr, false, st);
   if (groups > 1) {  // the direct grouped kernels: nothing to pair, defer or hand on
-    at::Tensor gdw = gconv2d_wgrad(dy, x, {w.size(0), w.size(1), w.size(2), w.size(3)}, stride, pad, groups, dw_out,
-                                   false);
+    const std::vector<int64_t> ws{w.size(0), w.size(1), w.size(2), w.size(3)};
+    const std::vector<int64_t> xs{x.size(0), x.size(1), x.size(2), x.size(3)};
+    const bool dw = is_depthwise(x, w, groups);  // dwconv.hip
+    at::Tensor gdw = dw ? dwconv2d_wgrad(dy, x, ws, stride, pad, dw_out, false)
+                        : gconv2d_wgrad(dy, x, ws, stride, pad, groups, dw_out, false);
     at::Tensor gdx;
     if (need_dx)
-      gdx = gconv2d_dgrad(dy, w, {x.size(0), x.size(1), x.size(2), x.size(3)}, stride, pad, groups, c10::nullopt);
+      gdx = dw ? dwconv2d_dgrad(dy, w, xs, stride, pad, c10::nullopt)
+               : gconv2d_dgrad(dy, w, xs, stride, pad, groups, c10::nullopt);
     return {gdx, gdw, db, dgamma, dbeta, at::Tensor(), at::Tensor(), dy_amax};
   }
   // x may carry zero-padded channels (RGB stem, see conv_bn_act_fwd); a grouped conv's x.size(1) != w.size(1) too

@@ -40,6 +40,14 @@ at::Tensor gconv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, std::vector<
                          int64_t pad, int64_t groups, const c10::optional<at::Tensor>& addend);
 at::Tensor gconv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, std::vector<int64_t> w_shape, int64_t stride,
                          int64_t pad, int64_t groups, const c10::optional<at::Tensor>& out, bool accumulate);
+// Depthwise 3x3 conv (groups == C == Co, pad 1, stride 1 or 2, C % 4 == 0) by the direct fp32 kernels of
+// dwconv.hip; w [C, 1, 3, 3]. dwconv2d_fwd returns conv2d_fwd's {y[, part, rows per part]}.
+std::vector<at::Tensor> dwconv2d_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
+                                     int64_t stride, int64_t pad, bool want_stats);
+at::Tensor dwconv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, std::vector<int64_t> in_shape, int64_t stride,
+                          int64_t pad, const c10::optional<at::Tensor>& addend);
+at::Tensor dwconv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, std::vector<int64_t> w_shape, int64_t stride,
+                          int64_t pad, const c10::optional<at::Tensor>& out, bool accumulate);
 std::vector<at::Tensor> conv_bn_act_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b,
                                         const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta,
                                         const c10::optional<at::Tensor>& running_mean,
